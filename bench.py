@@ -1,12 +1,21 @@
 """Benchmark of the denoise-training hot path on MI355X.
 
-python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2]
+python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c5] [--dump-outputs DIR] [--full]
 (N > 1: launched by torch.distributed.run, one rank per GPU over RCCL.)
 
 Prints ONE JSON line (rank 0): BASELINE.json's metric "denoise-train frames/sec
-(24 kHz, hop 300)" — frames = clips x 24000 / 300 — for the whole job, with
-a live `roofline` for the dominant kernel (HIP events on its launch stream) and
-a `cpu_baseline` (the oracle, timed on this host's cores on a bounded sample).
+(24 kHz, hop 300)" — frames = clips x 24000 / 300 — for the whole job.  A plain
+run sets up, warms up, times the K steps and prints that line.  --full adds
+what takes runs of its own: a live `roofline` for the dominant kernel (HIP
+events on its launch stream), the `fp32_companion` step, the `stft_kernel`
+probe and a `cpu_baseline` (the oracle, timed on this host's cores on a
+bounded sample); those keys are null in a plain run.
+
+--dump-outputs DIR writes, after the timed steps, what the timed step left its
+caller in the last step as DIR/<name>.npy (float32; host floats float64): the
+trained parameters, their gradients and the recorded loss totals (c2: the loss
+and the waveform gradient).  The inputs and the initial weights are seeded, so
+two builds run with the same arguments can be compared array for array.
 
 Workloads (BASELINE.json configs):
   c3 (default): configs[2] — one full denoise-trainer step (trainer/denoise.py):
@@ -84,6 +93,8 @@ def c2_setup(dev, B):
         sc, mg = stft(x, y)
         loss = 45.0 * mel(x, y) + 45.0 * (sc + mg)
         loss.backward()
+        step.loss = loss.detach()
+    step.x = x
     return step
 
 
@@ -313,7 +324,9 @@ def c5_setup(dev, B, world, local, dtype=torch.bfloat16):
 
     def step():
         with precision(dtype):
-            st.model_step(clean, mixed)
+            gen_loss, dis_loss = st.model_step(clean, mixed)[:2]
+        step.losses = (gen_loss.detach(), dis_loss.detach())
+    step.generator, step.discriminator = G, D
     return step
 
 
@@ -537,6 +550,68 @@ def stft_kernel_roofline(dev, B=2048):
                       "frac_of_copy_f4": round(nbytes / t_burst / 1e9 / f4_gbs, 4)}}
 
 
+DUMP_BUDGET = 48 << 20  # bytes of array data per dump (the files stay under 64 MB in all)
+
+
+def step_outputs(cfg, step):
+    """{name: tensor or float} of what the timed step left its caller after
+    its last run: per trained module the parameters (after the update) and
+    their gradients (as the optimizer consumed them), and the recorded losses
+    (c3: the trainer's running totals over every step run so far, warm-up
+    included; c2 / c5: the last step's loss values)."""
+    out = {}
+
+    def module(tag, m):
+        for k, p in m.named_parameters():
+            if p.requires_grad:
+                out[f"param.{tag}.{k}"] = p
+                if p.grad is not None:
+                    out[f"grad.{tag}.{k}"] = p.grad
+
+    if cfg == "c2":
+        out["loss"], out["grad.x"] = step.loss, step.x.grad
+    elif cfg == "c3":
+        module("generator", step.generator)
+        if hasattr(step, "flush_totals"):
+            step.flush_totals()  # graph replays accumulate on the device
+        totals = dict(step.trainer.total_train_loss.items())
+        for k in sorted(totals):
+            out["loss_total." + k.replace("/", ".")] = totals[k]
+    else:
+        module("generator", step.generator)
+        module("discriminator", step.discriminator)
+        out["loss.generator"], out["loss.discriminator"] = step.losses
+    return out
+
+
+def dump_outputs(dirname, named, budget=DUMP_BUDGET, seed=93):
+    """named values -> dirname/<name>.npy, float32 (plain floats: float64).
+    Past `budget` bytes in all, the largest arrays are cut to a common length:
+    a seeded sample of their flattened elements, the same indices (sorted) for
+    the same name and size in every run."""
+    import zlib
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {}
+    for k, v in named.items():
+        if torch.is_tensor(v):
+            arrays[k] = v.detach().to(device="cpu", dtype=torch.float32).contiguous().numpy()
+        else:
+            arrays[k] = np.asarray(v, dtype=np.float64)
+    sizes = sorted(a.size for a in arrays.values())
+    cap, left = None, budget // 4
+    for i, n in enumerate(sizes):  # the largest per-array length that keeps the sum within the budget
+        if n * (len(sizes) - i) > left:
+            cap = left // (len(sizes) - i)
+            break
+        left -= n
+    for k, a in arrays.items():
+        if cap is not None and a.size > cap:
+            rng = np.random.Generator(np.random.PCG64([seed, zlib.crc32(k.encode()), a.size]))
+            a = a.reshape(-1)[np.sort(rng.choice(a.size, size=cap, replace=False))]
+        np.save(os.path.join(dirname, k + ".npy"), a)
+    return len(arrays)
+
+
 def launch_cmd(n, port, argv):
     """torch.distributed.run command line for N local ranks of this script."""
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
@@ -601,8 +676,13 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3", choices=["c2", "c3", "c5"])
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: config's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fp32-companion", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the per-kernel roofline, the fp32 "
+                         "companion step, the STFT kernel probe and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left its caller as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-fp32-companion", action="store_true", help="with --full: leave the fp32 companion out")
     ap.add_argument("--eager", action="store_true",
                     help="c3: issue every launch from Python instead of replaying the step's HIP graph")
     args = ap.parse_args()
@@ -666,10 +746,14 @@ def main():
     timer = (_lib.KernelTimer([dom] + (["sel_resunit_fwd", "sel_resunit_bwd", "sel_resunit_bwd_wgrad",
                                         "sel_conv_wgrad_partials", "sel_wgrad_finish_many"]
                                        if cfg == "c3" else ["sel_stft_loss_bwd", "sel_mel_l1_fwd_grad"]))
-             if cfg != "c5" else None)  # C5: a serialised extra step below
+             if cfg != "c5" and args.full else None)  # C5: a serialised extra step below
     graphed = cfg == "c3" and hasattr(step, "graph")
     elapsed, per_step = _timed_steps(step, args.steps, world, dev, None if graphed else timer)
-    if graphed:
+    if args.dump_outputs and rank == 0:
+        # before anything below steps the model again
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, step_outputs(cfg, step))
+    if graphed and args.full:
         # per-launch HIP events cannot sit inside a replay: the roofline comes
         # from one eager step of the same trainer after the timed region (the
         # same kernels on the same shapes)
@@ -683,7 +767,7 @@ def main():
     frames_per_step = world * B * sr / HOP
     value = frames_per_step * args.steps / elapsed
     med_ms = float(np.median(per_step))
-    if cfg == "c5":
+    if cfg == "c5" and args.full:
         # the C5 step runs the 8 sub-discriminator chains on side streams: an
         # event pair around one launch there also spans what the other streams
         # run beside it, so the roofline comes from ONE extra step with the
@@ -702,14 +786,15 @@ def main():
             del os.environ["SEL_D_STREAMS"]
         else:
             os.environ["SEL_D_STREAMS"] = prev
-    roof = roofline(cfg, timer, dom, B, 1)  # the timer covered one step (C3: the last timed one)
-    if graphed:
+    # the timer covered one step (C3: the last timed one)
+    roof = roofline(cfg, timer, dom, B, 1) if args.full else None
+    if graphed and args.full:
         roof["timing"] = "one eager step after the timed graph replays (same kernels)"
-    if cfg == "c5":
+    if cfg == "c5" and args.full:
         roof["timing"] = "one extra step with the sub-discriminator chains serialised (SEL_D_STREAMS=0)"
 
     fp32 = None
-    if cfg == "c3" and not args.no_fp32_companion:
+    if cfg == "c3" and args.full and not args.no_fp32_companion:
         # the reference's own arithmetic (fp32 convs on the exact-fp32 MFMA path), same step
         step32 = c3_setup(dev, B, world, local, dtype=torch.float32)
         for _ in range(2):
@@ -720,9 +805,9 @@ def main():
                 "median_ms_per_step": round(float(np.median(per32)), 3)}
         del step32
 
-    stft_roof = stft_kernel_roofline(dev) if world == 1 and cfg != "c5" else None
+    stft_roof = stft_kernel_roofline(dev) if args.full and world == 1 and cfg != "c5" else None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         ncores = len(os.sched_getaffinity(0))
         ncores = min(ncores, int(os.environ.get("OMP_NUM_THREADS", ncores)))
         torch.set_num_threads(ncores)
@@ -736,7 +821,7 @@ def main():
             "metric": ("denoise-train frames/sec (24 kHz, hop 300)" if cfg != "c5"
                        else "GAN-mode denoise-train frames/sec (48 kHz, hop 300)"),
             "value": round(value, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3),
+            "warmup": args.warmup, "full": args.full, "ms_per_step": round(ms_per_step, 3),
             "median_ms_per_step": round(med_ms, 3),
             "value_at_median": round(frames_per_step / (med_ms * 1e-3), 1),
             "higher_is_better": True,

@@ -68,9 +68,12 @@ def test_bench_launcher_starts_world_size_ranks(tmp_path):
     (gloo, CPU): run the same torch.distributed.run line on a probe script."""
     import subprocess
     probe = tmp_path / "probe.py"
+    # one os.write per rank: the ranks share the launcher's stdout, and print()
+    # hands its arguments over piecewise, so two ranks' lines could interleave
     probe.write_text("import os, torch.distributed as d\n"
                      "d.init_process_group('gloo')\n"
-                     "print('RANK', os.environ['RANK'], os.environ['WORLD_SIZE'], d.get_world_size(), flush=True)\n"
+                     "os.write(1, ('RANK %s %s %d\\n' % (os.environ['RANK'], os.environ['WORLD_SIZE'],\n"
+                     "                                d.get_world_size())).encode())\n"
                      "d.destroy_process_group()\n")
     sys.path.insert(0, REPO)
     import bench
@@ -91,6 +94,40 @@ def test_bench_launcher_starts_world_size_ranks(tmp_path):
     assert out.returncode == 0, out.stderr[-2000:]
     lines = sorted(l for l in out.stdout.splitlines() if l.startswith("RANK"))
     assert lines == ["RANK 0 2 2", "RANK 1 2 2"], out.stdout
+
+
+def test_bench_dump_outputs_bounded_and_repeatable(tmp_path):
+    """bench.dump_outputs: float32 / float64 .npy files, whole arrays while they
+    fit the byte budget, else the largest cut to one common length by a seeded
+    sample that picks the same elements in every run."""
+    import numpy as np
+    sys.path.insert(0, REPO)
+    import bench
+    g = torch.Generator().manual_seed(0)
+    named = {"param.a": torch.randn(7, 3, generator=g), "grad.big": torch.randn(5000, generator=g).bfloat16(),
+             "grad.big2": torch.randn(40, 100, generator=g), "loss": 1.25}
+    assert bench.dump_outputs(str(tmp_path / "whole"), named) == 4
+    for k, v in named.items():
+        a = np.load(tmp_path / "whole" / (k + ".npy"))
+        if torch.is_tensor(v):
+            assert a.dtype == np.float32 and np.array_equal(a, v.float().numpy())
+        else:
+            assert a.dtype == np.float64 and a == v
+    budget = 4 * 2000
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), named, budget=budget)
+    total = 0
+    for k, v in named.items():
+        a, b = np.load(tmp_path / "s1" / (k + ".npy")), np.load(tmp_path / "s2" / (k + ".npy"))
+        assert np.array_equal(a, b)
+        total += a.size
+        if k.startswith("grad.big"):
+            flat = v.float().numpy().reshape(-1)
+            assert a.ndim == 1 and a.size < flat.size and np.isin(a, flat).all()
+        else:
+            assert a.shape == tuple(getattr(v, "shape", ()))
+    assert 4 * total <= budget and total > 1900
+    assert np.load(tmp_path / "s1" / "grad.big.npy").size == np.load(tmp_path / "s1" / "grad.big2.npy").size
 
 
 def test_set_epoch_reshuffles_distributed_shards():

@@ -4,8 +4,10 @@
 # by "|VAR=val|..." environment settings; "" = defaults; run
 # the list twice for an alternating A/B).  BENCH_ARGS: extra bench.py arguments
 # (e.g. "--config c5 --steps 10 --warmup 2"; default: C3, 30 steps).
+# Logs go to $BENCH_OUT (default: bench_out/ in the repository).
 set -o pipefail
-cd $GRAFT_REPO_ROOT; mkdir -p gpurun_out
+cd "$(dirname "$0")/.."
+OUT=${BENCH_OUT:-bench_out}; mkdir -p $OUT
 ARGS=${BENCH_ARGS:---steps 30 --warmup 5}
 i=0
 for cfg in "$@"; do
@@ -14,6 +16,7 @@ for cfg in "$@"; do
   envs=""
   [[ "$cfg" == *"|"* ]] && envs=${cfg#*|} && envs=${envs//|/ }
   tag=${cfg//[,|=\/]/_}; tag=${tag:0:60}
-  env SEL_TUNE=$tune $envs timeout -k 10 300 python bench.py $ARGS --no-cpu-baseline --no-fp32-companion > gpurun_out/ab_${i}_$tag.log 2>&1 || exit 1
-  echo "cfg=$cfg $(tail -1 gpurun_out/ab_${i}_$tag.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print("mean", d["ms_per_step"], "median", d["median_ms_per_step"], d["value"], d["roofline"]["kernel"], d["roofline"]["frac"])')"
+  # --full: the roofline of the dominant kernel is read below
+  env SEL_TUNE=$tune $envs timeout -k 10 300 python bench.py $ARGS --full --no-cpu-baseline --no-fp32-companion > $OUT/ab_${i}_$tag.log 2>&1 || exit 1
+  echo "cfg=$cfg $(tail -1 $OUT/ab_${i}_$tag.log | python -c 'import json,sys; d=json.loads(sys.stdin.read()); print("mean", d["ms_per_step"], "median", d["median_ms_per_step"], d["value"], d["roofline"]["kernel"], d["roofline"]["frac"])')"
 done
