@@ -103,6 +103,24 @@ def test_stft_errors(S, gpu):
         S.stft_mag(torch.randn(2, 4000, device=gpu), 1000, 100, 1000, torch.hann_window(1000, device=gpu))
     with pytest.raises(RuntimeError, match="CPU"):
         S.stft_mag(torch.randn(2, 4000), 1024, 120, 600, torch.hann_window(600))
+    # the other host limits of check_frame (spectral.hip)
+    x = torch.randn(2, 4000, device=gpu)
+    with pytest.raises(RuntimeError, match=r"win_length=1200 must be in \(0, n_fft=1024\]"):
+        S.stft_mag(x, 1024, 120, 1200, torch.hann_window(1200, device=gpu))
+    for n in (128, 4096):
+        with pytest.raises(RuntimeError, match=rf"n_fft={n} outside \[256, 2048\]"):
+            S.stft_mag(x, n, n // 4, n, torch.hann_window(n, device=gpu))
+    # hop = 0 and a 2^29-sample batch straight through the C entry point (the
+    # Python wrapper sizes its output from them); both are refused before any
+    # launch, so the buffers are never addressed
+    from sel import _lib as L
+    win = torch.hann_window(600, device=gpu)
+    mag = torch.empty(16, device=gpu)
+    with pytest.raises(RuntimeError, match="hop must be > 0"):
+        L.call("sel_stft_mag_fwd", L.ptr(x), 2, 4000, 1024, 0, 600, L.ptr(win), 1e-7, L.ptr(mag), L.stream())
+    with pytest.raises(RuntimeError, match="exceeds 2 GiB per call"):
+        L.call("sel_stft_mag_fwd", L.ptr(x), 1 << 15, 1 << 14, 1024, 120, 600, L.ptr(win), 1e-7, L.ptr(mag),
+               L.stream())
 
 
 def test_stft_losses_match_reference_golden(gpu, stft_g):

@@ -4,7 +4,9 @@ own layer shapes.  Knobs covered elsewhere: 0 and 47/50/51/52 (tile variants
 and the sample-tile kernel, test_gpu_c3), 1/3/4/5/11/54/55 (test_gpu_conv; 54 /
 55: the fp32 kernels), 2 and 39 (RVQ kernels, test_gpu_model), 9/18/19/21/22/26/
 30 (discriminator variants, test_gpu_dconv_variants / test_gpu_c5), 24
-(test_gpu_conv).  The rest are here:
+(test_gpu_conv), 14 (fixed frame-loop passes of the spectral frame kernels:
+test_gpu_spectral_edges runs every one at 2, 3 and 5 passes against the fp64
+oracle and bit-for-bit against the default plan).  The rest are here:
 
 * generator (C3 widths, B = 2 x 1 s @ 24 kHz, bf16, full fwd + bwd): 6 (thin
   kernel instances on their alternative tile rows), 7 (thin kernel off: tiled
