@@ -105,6 +105,9 @@ SIGNATURES = {
     "sel_gan_workspace": (SZ, []),
     "sel_gan_reduce": (I32, [I32, I32, P, P, P, P, P, P, I32, F32, ctypes.c_double, I32, P, P, SZ, P]),
     "sel_gan_grad": (I32, [I32, I32, P, P, P, P, P, P, I32, F32, P, F32, P, P, I32, P]),
+    "sel_hfg_conv_kernel": (I32, [P, I32, I32]),
+    "sel_hfg_conv_fwd": (I32, [P, I32, I32, P, P, P, P, P, P]),
+    "sel_hfg_reslayer_fwd": (I32, [P, I32, P, P, P, P, P, P, P]),
 }
 
 _lock = threading.Lock()

@@ -114,6 +114,16 @@ SYMAD_24MEL_NDOSNR = dict(SYMAD_24MEL, **_NDO, initial_model="24kHz-NDR08-NDRD01
                           step=55830, lambda_snr_loss=45.0)
 SYMAD_CUSTOM = dict(SYMAD_24MEL, **_NDO, sample_rate=48000, step=55830, batch_size=16)
 
+# HiFi-GAN vocoder generators (config/vocoder/AudioDec_v{0,1,2}_symAD_vctk_48000_hop300_clean.yaml:28-47,
+# generator_params; `stats` names a statistics file of the recipe and is left to the caller)
+_VOCODER = dict(in_channels=64, out_channels=1, channels=512, kernel_size=7, upsample_scales=[5, 5, 4, 3],
+                upsample_kernel_sizes=[10, 10, 8, 6], bias=True, use_additional_convs=True,
+                nonlinear_activation="LeakyReLU", nonlinear_activation_params=dict(negative_slope=0.1),
+                use_weight_norm=True, stats=None)
+VOCODER_V0 = dict(_VOCODER, resblock_kernel_sizes=[3, 7, 11], resblock_dilations=[[1, 3, 5]] * 3, groups=1)
+VOCODER_V1 = dict(_VOCODER, resblock_kernel_sizes=[11], resblock_dilations=[[1, 3, 5]], groups=3)
+VOCODER_V2 = dict(_VOCODER, resblock_kernel_sizes=[3], resblock_dilations=[[1, 3, 5]], groups=3)
+
 CONFIGS = {"symAD_libritts_24000_hop300": SYMAD_LIBRITTS_24K_DENOISE, "symAD_24Mel": SYMAD_24MEL,
            "symAD_24MelNDO": SYMAD_24MEL_NDO, "symAD_24MelNDOSNR": SYMAD_24MEL_NDOSNR,
            "symAD_custom": SYMAD_CUSTOM, "symAD_vctk_48000_hop300": SYMAD_VCTK_48K_GAN}

@@ -499,6 +499,73 @@ int sel_gan_grad(int kind, int dtype, const void* a, const int64_t* a_size, cons
                  const int64_t* b_size, const int64_t* b_stride, int ndim, float target, const float* gscale,
                  float mult, void* grad, const int64_t* g_stride, int accumulate, sel_stream_t stream);
 
+/* ---- HiFi-GAN vocoder generator, inference (models/vocoder/HiFiGAN.py:28-305,
+ * modules/residual_block.py:23-106, modules/multi_fusion.py:23-141) ----------
+ * Every conv of the generator is ONE grouped primitive with the channels-last
+ * lowering of sel_conv_desc (row(m,k) = b*T + t + k*dil - pad, t = m % T_out,
+ * b = m / T_out; SEL_PAD_ZERO / SEL_PAD_REPLICATE; packed weights Wp[N][K][C/G],
+ * i.e. per group g the block Wp[g*N/G .. (g+1)*N/G): sel_pack_weight kinds
+ * SEL_PACK_FWD (cout = N, cin = C/G) and SEL_PACK_CONVT serve it):
+ *   out[m, n] = epi( sum_{k<K} sum_{c<C/G} Wp[n][k][c] * act(in[row(m,k), g*in_group_stride + c]) ),
+ *   g = n / (N/G);
+ *   act(v) = v >= 0 ? v : act_slope * v  (act_slope 1 = identity); input rows
+ *   t < act_skip of each sample are taken as they are (a streaming buffer that
+ *   already holds activated rows, conv_layer.py:144-147 fed by HiFiGAN.py:289);
+ *   epi(v): v += bias[n % bias_period]; v += res[m, g*res_group_stride + n % (N/G)]
+ *   when res != NULL; v = tanh(v) when tanh_out; v *= out_scale; v += out[m, n]
+ *   (the value already there) when accumulate.
+ * in_group_stride is C/G (input rows of pitch C), or 0: every group reads the
+ * same C/G channels of an input of pitch C/G -- MultiGroupConv1d's
+ * x.repeat(1, groups, 1) (multi_fusion.py:124) without the copy; res_group_stride
+ * likewise (N/G with pitch N, or 0 with pitch N/G).  T input rows and T_out
+ * output rows per sample (T_out 0: = T); T_out < T with pad 0 is the valid
+ * conv of a streaming step.  Rows outside [0, T) of the sample read 0, or the
+ * sample's first / last row in replicate mode: never another sample's rows.
+ * CONTRACT (bf16): the prologue result act(v) is rounded to bf16 once before
+ * the matrix multiply; products accumulate in fp32; res, the accumulated
+ * out and the result are rounded to the output type once each.
+ * in_dtype / out_dtype: fp32 -> fp32, bf16 -> bf16 or fp32; res and an
+ * accumulated out have the output type. */
+typedef struct sel_hfg_conv_desc {
+  int64_t rows;             /* B * T_out */
+  int32_t T;                /* input rows per sample */
+  int32_t T_out;            /* output rows per sample, 0: T */
+  int32_t C, N;             /* in / out channels over all groups */
+  int32_t K, dil, pad;
+  int32_t pad_mode;         /* SEL_PAD_* */
+  int32_t groups;
+  int32_t in_group_stride;  /* C/G or 0 */
+  int32_t res_group_stride; /* N/G or 0 */
+  int32_t bias_period;      /* 0: no bias */
+  int32_t act_skip;
+  int32_t tanh_out;
+  int32_t accumulate;
+  float act_slope;
+  float out_scale;
+} sel_hfg_conv_desc;
+/* kernel a launch of this shape takes: 0 = one thread per output (fp32, thin
+ * outputs with N/G <= 4, tiles that do not fit LDS), 1 / 2 / 4 = the bf16
+ * matrix-core tile of 64 rows x 16 / 32 / 64 channels; negative: bad descriptor */
+int sel_hfg_conv_kernel(const sel_hfg_conv_desc* d, int in_dtype, int out_dtype);
+int sel_hfg_conv_fwd(const sel_hfg_conv_desc* d, int in_dtype, int out_dtype, const void* in, const void* wpack,
+                     const float* bias, const void* res, void* out, sel_stream_t stream);
+/* Fused residual layer (residual_block.py:93-97, one launch per layer):
+ *   out = epi( x + conv2_{K,1}(act(conv1_{K,dil}(act(x)) + b1)) + b2 ),
+ * d1 describes conv1 (causal zero pad (K-1)*dil, C = N, groups, in_group_stride,
+ * act_slope) and the final epilogue (x is the residual: res_group_stride 0
+ * exactly when in_group_stride is 0; out_scale, accumulate); conv2 has the same
+ * K and groups at dilation 1; b1 and b2 both given or bias_period 0.  The conv1
+ * tile with the K-1 halo rows conv2 needs stays in LDS.  bf16, C/G in {32, 64},
+ * K in {3, 7, 11}, any dil whose tiles fit LDS; bit-identical to the two
+ * sel_hfg_conv_fwd launches it replaces (same MFMA sequence, h rounded to bf16
+ * where the first launch would store it).  Returns SEL_ERR_UNSUPPORTED for every
+ * other shape and for the (C/G, K) pairs on which two launches measured no
+ * slower -- the caller then issues the two launches.  sel_tune key 71: 1 =
+ * always SEL_ERR_UNSUPPORTED (the two-launch path), 2 = fused wherever the
+ * shape allows (A/B runs, tests). */
+int sel_hfg_reslayer_fwd(const sel_hfg_conv_desc* d1, int dtype, const void* x, const void* w1pack, const float* b1,
+                         const void* w2pack, const float* b2, void* out, sel_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
