@@ -3,10 +3,11 @@
 * ``Generator`` / ``StreamGenerator`` (:28-305): the causal HiFi-GAN vocoder
   generator of the AudioDec baseline (encoder -> projector -> quantizer ->
   vocoder) and of the streaming codec's decoders.  Same constructor arguments,
-  defaults, asserts, sub-module names and ``state_dict`` keys.  Inference only:
-  every conv runs the grouped LeakyReLU-fused HIP primitive of sel.hfgops;
-  ``forward`` raises NotImplementedError when a gradient would be required
-  (vocoder training is not built).
+  defaults, asserts, sub-module names and ``state_dict`` keys.  Every conv runs
+  the grouped LeakyReLU-fused HIP primitive of sel.hfgops.  Inference by
+  default: ``forward`` raises NotImplementedError when a gradient would be
+  required, unless ``enable_training()`` opted in to the training path (the
+  backward kernels of the same primitive, trainer/vocoder.py).
 * ``Discriminator`` (:308-395): MSD + MPD, outputs concatenated (MSD first).
 """
 import logging
@@ -25,6 +26,8 @@ from sel.streams import run_concurrent
 
 class Generator(nn.Module):
     """HiFiGAN causal generator module."""
+
+    _training_enabled = False   # enable_training()
 
     def __init__(self, in_channels=80, out_channels=1, channels=512, kernel_size=7, upsample_scales=(8, 8, 2, 2),
                  upsample_kernel_sizes=(16, 16, 4, 4), resblock_kernel_sizes=(3, 7, 11),
@@ -96,18 +99,32 @@ class Generator(nn.Module):
         One primitive launch per conv: LeakyReLU(0.1) before every conv,
         LeakyReLU(0.01) before the output conv and tanh after it run inside
         the kernels (HiFiGAN.py:141-161)."""
-        HF.require_inference(self, c)
+        train = self._training_enabled and HF.needs_grad(self, c)
+        if not train:
+            HF.require_inference(self, c)
         if self.norm:
             c = (c.transpose(2, 1) - self.mean) / self.scale
             c = c.transpose(2, 1)
-        x = HF.causal(HF.enter(c), self.input_conv)
+        if train:
+            return HF.generator_train(self, self._run, c)
+        return self._run(HF.enter(c)).transpose(1, 2)
+
+    def enable_training(self, flag=True):
+        """Opt in to (or out of) the training path: with it on, a ``forward`` that
+        needs a gradient runs the backward kernels of sel.hfgops instead of
+        raising.  A plain attribute: no parameter, buffer or state_dict key."""
+        self._training_enabled = bool(flag)
+        return self
+
+    def _run(self, x):
+        """the launch sequence of forward on channels-last x (B, T, in_channels) -> (B, T', out_channels) fp32"""
+        x = HF.causal(x, self.input_conv)
         up = HF.slope_of(self.activation_upsamples)
         for i in range(self.num_upsamples):
             x = HF.upsample(x, self.upsamples[i], up)
             x = self._block(i, x, False)
-        x = HF.causal(x, self.output_conv, HF.slope_of(self.activation_output1), tanh=True,
-                      out_dtype=torch.float32)
-        return x.transpose(1, 2)
+        return HF.causal(x, self.output_conv, HF.slope_of(self.activation_output1), tanh=True,
+                         out_dtype=torch.float32)
 
     def reset_parameters(self):
         """Reset parameters (the official implementation's initialisation,

@@ -108,6 +108,10 @@ SIGNATURES = {
     "sel_hfg_conv_kernel": (I32, [P, I32, I32]),
     "sel_hfg_conv_fwd": (I32, [P, I32, I32, P, P, P, P, P, P]),
     "sel_hfg_reslayer_fwd": (I32, [P, I32, P, P, P, P, P, P, P]),
+    "sel_hfg_conv_bwd_kernel": (I32, [P, I32, I32, I32]),
+    "sel_hfg_conv_bwd_data": (I32, [P, I32, I32, P, P, P, P, P, F32, P, P]),
+    "sel_hfg_conv_wgrad_workspace": (SZ, [P, I32, I32]),
+    "sel_hfg_conv_wgrad": (I32, [P, I32, I32, P, P, P, P, P, P, SZ, P]),
 }
 
 _lock = threading.Lock()

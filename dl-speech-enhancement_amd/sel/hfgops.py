@@ -1,5 +1,6 @@
-"""Inference ops of the HiFi-GAN vocoder generator over libsel.so's grouped
-LeakyReLU-fused conv primitive (csrc/hifigan.hip, include/sel.h sel_hfg_conv_desc).
+"""Ops of the HiFi-GAN vocoder generator over libsel.so's grouped LeakyReLU-fused
+conv primitive (csrc/hifigan.hip, include/sel.h sel_hfg_conv_desc) and its
+backward (csrc/hifigan_bwd.hip).
 
 Reference semantics (file:line under the reference root):
 * Generator / StreamGenerator   models/vocoder/HiFiGAN.py:28-305
@@ -16,7 +17,18 @@ inner module is called.  This package never calls it, so ``weight`` is stale
 after load_state_dict; the packs here are built from g * v / ||v|| (norm over
 all dims but 0) and cached by the parameters' versions.
 
-Training the vocoder (dgrad, grouped wgrad, weight-norm backward) is not built:
+Training (``generator_train``): the whole generator is ONE autograd node.  Its
+forward issues the launches of the no-grad forward (two launches per residual
+layer) while a tape records, per conv, the descriptor, the input x and -- for
+the tanh output conv only -- the fp32 output.  Its backward walks the tape in
+reverse with sel_hfg_conv_bwd_data / sel_hfg_conv_wgrad: LeakyReLU', tanh', the
+scales, the skip adds, the MultiReceptiveField fan-in and MultiGroupConv1d's
+group sum all run in those kernels' prologues / epilogues, so no
+activation-sized elementwise pass and no autograd in-place write exists.  Weight
+norm stays in torch on weight-sized tensors: the node's weight inputs are
+g * v / ||v|| computed with grad enabled, and its packs are rebuilt from them on
+every call (the version-keyed cache below serves inference only: fused Adam does
+not bump versions).  Without ``Generator.enable_training()``,
 ``require_inference`` raises when a gradient would be needed.
 """
 import ctypes
@@ -25,6 +37,7 @@ import weakref
 
 import torch
 import torch.nn.functional as F
+from torch.optim.optimizer import register_optimizer_step_post_hook
 
 from . import _lib as L
 from . import convops as CO
@@ -46,12 +59,17 @@ def make_desc(rows, T, C, N, K, dil=1, pad=0, pad_mode=CO.PAD_ZERO, groups=1, sh
                    0 if shared_res else N // groups, bias_period, act_skip, int(tanh), int(accumulate), slope, scale)
 
 
+def needs_grad(module, x):
+    return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters()))
+
+
 def require_inference(module, x):
-    """The vocoder is inference-only: no silent torch fallback for a training step."""
-    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in module.parameters())):
+    """Inference unless training was enabled: no silent torch fallback for a training step."""
+    if needs_grad(module, x):
         raise NotImplementedError(
             "the HiFi-GAN vocoder generator is built for inference only: call it under torch.no_grad() "
-            "(or with requires_grad False on the input and every parameter); vocoder training is not implemented")
+            "(or with requires_grad False on the input and every parameter), or opt in to the training path "
+            "with enable_training()")
 
 
 def slope_of(act):
@@ -78,6 +96,7 @@ def _signature(m):
     return tuple((p.data_ptr(), p._version, p.device) for p in ps)
 
 
+_TAPE = threading.local()   # .tape: the recorder of a training forward in progress (further down)
 _PACKS = weakref.WeakKeyDictionary()   # inner conv module -> {(kind, stride, dtype): (signature, packed)}
 _PACK_LOCK = threading.Lock()
 
@@ -86,6 +105,9 @@ def packed(m, kind, stride, dtype):
     """Packed Wp (dtype) of the inner conv module m, refreshed when its
     parameters change (version counters / storage); code that writes a weight
     through ``.data`` must call ``invalidate()``."""
+    tape = getattr(_TAPE, "tape", None)
+    if tape is not None:
+        return tape.pack(m, kind, stride, dtype)
     sig = _signature(m)
     key = (kind, stride, dtype)
     with _PACK_LOCK:
@@ -103,6 +125,23 @@ def packed(m, kind, stride, dtype):
 def invalidate():
     with _PACK_LOCK:
         _PACKS.clear()
+
+
+def _optimizer_stepped(optimizer, args, kwargs):
+    """Global torch.optim post-step hook (as sel.convops has for its packs): a
+    fused Adam writes the parameters without bumping their version counters, so
+    the inference packs of every conv the optimizer updated are dropped -- the
+    no-grad forward of the vocoder trainer's discriminator step follows the
+    generator update directly."""
+    if not _PACKS:
+        return
+    stepped = {id(p) for g in optimizer.param_groups for p in g["params"] if p.grad is not None}
+    with _PACK_LOCK:
+        for m in [m for m in _PACKS if any(id(p) in stepped for p in m.parameters(recurse=False))]:
+            del _PACKS[m]
+
+
+register_optimizer_step_post_hook(_optimizer_stepped)
 
 
 # ---- the primitive -----------------------------------------------------------------------------
@@ -141,6 +180,9 @@ def prim(desc, x, wp, bias=None, res=None, out=None, out_dtype=None):
         assert bias.dtype == torch.float32 and bias.is_contiguous()
     L.call("sel_hfg_conv_fwd", ctypes.byref(desc), CO._code(x.dtype), CO._code(out_dtype), L.ptr(x), L.ptr(wp),
            L.ptr(bias), L.ptr(res), L.ptr(out), L.stream(), meta=lambda: _meta(desc, x, wp, res, out))
+    tape = getattr(_TAPE, "tape", None)
+    if tape is not None:
+        tape.record(desc, x, wp, res, out)
     return out
 
 
@@ -246,6 +288,8 @@ def reslayer(x, l1, l2, slope, shared=False, scale=1.0, out=None):
     """One residual layer x + conv2(act(conv1(act(x)))) in one launch
     (sel_hfg_reslayer_fwd), or None where the library keeps two launches."""
     c1, c2 = l1.conv, l2.conv
+    if getattr(_TAPE, "tape", None) is not None:
+        return None   # the training forward stores h: two launches, bit-identical to the fused layer
     if x.dtype != torch.bfloat16 or c2.kernel_size != c1.kernel_size or c2.dilation[0] != 1 \
             or c2.groups != c1.groups or (c1.bias is None) != (c2.bias is None):
         return None
@@ -319,3 +363,215 @@ def mrf(x, blocks, slope, stream=False):
         y = resblock(x, blk, slope, stream=stream, scale=1.0 / nb, out=out)
         out = y if out is None else out
     return out
+
+
+# ---- backward of the primitive ---------------------------------------------------------------
+TUNE_WGRAD_SPLIT = 72   # sel_tune key: > 0 forces the row-split count of sel_hfg_conv_wgrad
+BWD_DATA_NAMES = {0: "k_bwd_data_valu", 1: "k_bwd_data_mfma<1>", 2: "k_bwd_data_mfma<2>", 4: "k_bwd_data_mfma<4>"}
+WGRAD_NAMES = {0: "k_wgrad_valu", 1: "k_wgrad_mfma"}
+
+
+def dgrad_pack(wp, groups):
+    """Wp[N][K][C/G] -> Wd[G][C/G][K][N/G]: the same values with the reduction axis
+    of the data gradient contiguous (a weight-sized permute, no rounding)."""
+    N, K, Cg = wp.shape
+    return wp.view(groups, N // groups, K, Cg).permute(0, 3, 2, 1).contiguous()
+
+
+def _nbytes(*ts):
+    return sum(t.numel() * t.element_size() for t in ts if t is not None)
+
+
+def bwd_data(desc, gout, wd, x=None, out=None, gskip=None, skip_scale=0.0, gin=None, dtype=None):
+    """sel_hfg_conv_bwd_data; returns gin (B, T, C or C/G), accumulated into the
+    given `gin` when desc.accumulate."""
+    L.need_device(gout, wd, x, out, gskip, gin)
+    dtype = dtype or wd.dtype
+    cin = desc.C if desc.in_group_stride else desc.C // desc.groups
+    B = desc.rows // desc.T
+    assert gout.is_contiguous() and gout.numel() == desc.rows * desc.N and wd.dtype == dtype and wd.is_contiguous()
+    assert x is None or (x.is_contiguous() and x.dtype == dtype and x.numel() == desc.rows * cin)
+    assert out is None or (out.is_contiguous() and out.dtype == gout.dtype and out.numel() == gout.numel())
+    assert gskip is None or (gskip.is_contiguous() and gskip.dtype == dtype and gskip.numel() == desc.rows * desc.C)
+    if gin is None:
+        assert not desc.accumulate
+        gin = torch.empty((B, desc.T, cin), dtype=dtype, device=gout.device)
+    else:
+        assert gin.is_contiguous() and gin.dtype == dtype and gin.numel() == desc.rows * cin
+
+    def meta():
+        kid = L.lib().sel_hfg_conv_bwd_kernel(ctypes.byref(desc), CO._code(dtype), CO._code(gout.dtype), 0)
+        nb = _nbytes(gout, wd, x if desc.act_slope != 1.0 else None, out if desc.tanh_out else None, gskip, gin,
+                     gin if desc.accumulate else None)
+        return (f"{BWD_DATA_NAMES.get(kid, 'k_bwd_data')}[{dtype}]", nb,
+                2.0 * desc.rows * desc.N * desc.K * (desc.C // desc.groups))
+
+    L.call("sel_hfg_conv_bwd_data", ctypes.byref(desc), CO._code(dtype), CO._code(gout.dtype), L.ptr(gout), L.ptr(out),
+           L.ptr(x), L.ptr(wd), L.ptr(gskip), float(skip_scale), L.ptr(gin), L.stream(), meta=meta)
+    return gin
+
+
+def wgrad(desc, gout, x, out=None):
+    """sel_hfg_conv_wgrad; returns (gWp fp32 (N, K, C/G), gbias fp32 (bias_period,) or None)."""
+    L.need_device(gout, x, out)
+    cin = desc.C if desc.in_group_stride else desc.C // desc.groups
+    assert gout.is_contiguous() and gout.numel() == desc.rows * desc.N
+    assert x.is_contiguous() and x.numel() == desc.rows * cin
+    assert out is None or (out.is_contiguous() and out.dtype == gout.dtype and out.numel() == gout.numel())
+    codes = (CO._code(x.dtype), CO._code(gout.dtype))
+    nbytes = L.lib().sel_hfg_conv_wgrad_workspace(ctypes.byref(desc), *codes)
+    ws = L.workspace(nbytes, x.device)
+    gwp = torch.empty((desc.N, desc.K, desc.C // desc.groups), dtype=torch.float32, device=x.device)
+    gb = torch.empty((desc.bias_period,), dtype=torch.float32, device=x.device) if desc.bias_period else None
+
+    def meta():
+        kid = L.lib().sel_hfg_conv_bwd_kernel(ctypes.byref(desc), *codes, 1)
+        return (f"{WGRAD_NAMES.get(kid, 'k_wgrad')}[{x.dtype}]",
+                _nbytes(gout, x, out if desc.tanh_out else None, gwp, gb) + 2 * nbytes,
+                2.0 * desc.rows * desc.N * desc.K * (desc.C // desc.groups))
+
+    L.call("sel_hfg_conv_wgrad", ctypes.byref(desc), *codes, L.ptr(gout), L.ptr(out), L.ptr(x), L.ptr(gwp), L.ptr(gb),
+           L.ptr(ws), nbytes, L.stream(), meta=meta)
+    return gwp, gb
+
+
+# ---- training: one autograd node per generator -----------------------------------------------
+def effective_weight_train(m):
+    """effective_weight with grad enabled: torch's weight-norm formula on the
+    weight-sized parameters (g * v / ||v||, norm over all dims but 0), or the
+    plain weight after remove_weight_norm()."""
+    g, v = getattr(m, "weight_g", None), getattr(m, "weight_v", None)
+    if g is None or v is None:
+        return m.weight
+    return v * (g / v.norm(2, dim=tuple(range(1, v.dim())), keepdim=True))
+
+
+def inner_convs(module):
+    """the nn.Conv1d / nn.ConvTranspose1d modules of a generator, in module order"""
+    return [m for m in module.modules() if isinstance(m, (torch.nn.Conv1d, torch.nn.ConvTranspose1d))]
+
+
+class _Record:
+    __slots__ = ("desc", "x", "out", "okey", "reskey", "mod", "wd", "kind", "stride")
+
+
+class _Tape:
+    """Recorder of one training forward: per launch the descriptor, the input x,
+    the fp32 output of a tanh conv, and the identities (storage addresses; every
+    conv output stays alive as a later conv's saved x) that tie the launches into
+    a dataflow graph for the reverse walk."""
+
+    def __init__(self, weights):
+        self.weights = weights    # inner conv module -> fp32 effective weight
+        self.packs = {}           # (module, kind, stride, dtype) -> (wp, wd)
+        self.by_wp = {}           # wp address -> (module, kind, stride, wd)
+        self.records = []
+
+    def pack(self, m, kind, stride, dtype):
+        key = (m, kind, stride, dtype)
+        hit = self.packs.get(key)
+        if hit is None:
+            wp = CO.pack(kind, self.weights[m], stride, dtype)
+            groups = m.groups if kind == CO.PACK_FWD else 1
+            hit = self.packs[key] = (wp, dgrad_pack(wp, groups))
+            self.by_wp[wp.data_ptr()] = (m, kind, stride, hit[1])
+        return hit[0]
+
+    def record(self, desc, x, wp, res, out):
+        r = _Record()
+        r.desc, r.x, r.okey = desc, x, out.data_ptr()
+        r.out = out if desc.tanh_out else None
+        r.reskey = res.data_ptr() if res is not None else None
+        r.mod, r.kind, r.stride, r.wd = self.by_wp[wp.data_ptr()]
+        self.records.append(r)
+
+
+def _copy_desc(d, **kw):
+    c = HfgDesc.from_buffer_copy(d)
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+def tape_backward(tape, gy, x0, need_x0):
+    """Reverse walk of a training forward.  gy: gradient of the last launch's
+    output, (rows, N).  Returns ({inner conv module: (gW torch layout, gbias)},
+    gradient of x0 or None).  A gradient buffer is keyed by the forward tensor it
+    belongs to: every launch that read that tensor accumulates into it in its own
+    epilogue, and every launch that accumulated into one output buffer reads the
+    same gout."""
+    grads = {tape.records[-1].okey: gy}
+    gws = {}
+    pending = None   # (address of res, gout, out_scale): consumed by the launch that read the same tensor as x
+    x0key = x0.data_ptr()
+    for r in reversed(tape.records):
+        d = r.desc
+        gout = grads[r.okey] if d.accumulate else grads.pop(r.okey)
+        gwp, gb = wgrad(d, gout, r.x, r.out)
+        w = tape.weights[r.mod]
+        gw = CO.unpack(r.kind, gwp, tuple(w.shape), r.stride)
+        assert r.mod not in gws
+        gws[r.mod] = (gw, gb)
+        if r.reskey is not None:
+            assert pending is None, "a residual is always the input of the layer it closes"
+            pending = (r.reskey, gout, d.out_scale)
+        xkey = r.x.data_ptr()
+        if xkey == x0key and not need_x0:
+            continue
+        gskip, sscale = None, 0.0
+        if pending is not None and pending[0] == xkey:   # else: conv2 of a layer, whose conv1 comes next
+            _, gskip, sscale = pending
+            pending = None
+        gin = grads.get(xkey)
+        bd = _copy_desc(d, accumulate=int(gin is not None))
+        if gin is None:
+            gin = torch.empty(r.x.shape, dtype=r.x.dtype, device=r.x.device)
+        grads[xkey] = bwd_data(bd, gout, r.wd, r.x, r.out, gskip, sscale, gin)
+    assert pending is None
+    return gws, grads.get(x0key)
+
+
+class _GeneratorFn(torch.autograd.Function):
+    """forward(run, mods, c, *tensors): run(x0) is the generator's launch sequence
+    on the channels-last input; tensors = per inner conv its effective weight
+    and bias (or None), in the order of mods."""
+
+    @staticmethod
+    def forward(ctx, run, mods, c, *tensors):
+        weights = {m: tensors[2 * i].detach() for i, m in enumerate(mods)}
+        tape = _Tape(weights)
+        x0 = enter(c)
+        _TAPE.tape = tape
+        try:
+            y = run(x0)            # (B, T, out_channels) fp32
+        finally:
+            _TAPE.tape = None
+        tape.packs, tape.by_wp = {}, {}   # the forward packs are not needed again (Wd lives in the records)
+        ctx.tape, ctx.x0, ctx.mods = tape, x0, mods
+        ctx.c_dtype = c.dtype
+        return y.transpose(1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        tape, mods = ctx.tape, ctx.mods
+        last = tape.records[-1].desc
+        gy = g.transpose(1, 2).contiguous().view(last.rows, last.N)
+        gws, gx0 = tape_backward(tape, gy, ctx.x0, ctx.needs_input_grad[2])
+        ctx.tape = None
+        out = []
+        for i, m in enumerate(mods):
+            gw, gb = gws.get(m, (None, None))
+            out += [gw if ctx.needs_input_grad[3 + 2 * i] else None, gb if ctx.needs_input_grad[4 + 2 * i] else None]
+        gc = gx0.transpose(1, 2).to(ctx.c_dtype) if gx0 is not None else None
+        return (None, None, gc, *out)
+
+
+def generator_train(module, run, c):
+    """Differentiable run(enter(c)) for a generator `module` whose convs all go
+    through this file's primitive: gradients reach c and every parameter."""
+    L.need_device(c)
+    mods = inner_convs(module)
+    tensors = []
+    for m in mods:
+        tensors += [effective_weight_train(m), m.bias]
+    return _GeneratorFn.apply(run, mods, c, *tensors)

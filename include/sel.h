@@ -566,6 +566,63 @@ int sel_hfg_conv_fwd(const sel_hfg_conv_desc* d, int in_dtype, int out_dtype, co
 int sel_hfg_reslayer_fwd(const sel_hfg_conv_desc* d1, int dtype, const void* x, const void* w1pack, const float* b1,
                          const void* w2pack, const float* b2, void* out, sel_stream_t stream);
 
+/* ---- HiFi-GAN vocoder generator, backward of the grouped primitive ---------
+ * Same descriptor, same channels-last lowering.  Write the forward as
+ *   out = prev*[accumulate] + out_scale * tanh?( conv(act(x)) + bias + res );
+ * gpre = out_scale * gout * (1 - out^2 when tanh_out) is the gradient at the
+ * conv's own output (before bias and res).  Training never streams: T_out not in
+ * {0, T} or act_skip != 0 returns SEL_ERR_UNSUPPORTED.  Descriptors are validated
+ * before any device work.  in_dtype is the type of x, the weights and gin;
+ * out_dtype that of gout and the saved out (fp32 for the tanh output conv).
+ *
+ * sel_hfg_conv_bwd_data: the exact adjoint of the forward gather, then the
+ * activation derivative, then the skip:
+ *   gin[b, s, g*igs + c] = act'(x[b,s,.]) * sum_{(t,k): in_row(t + k*dil - pad) = s} sum_{n in group g}
+ *                          W[n][k][c] * gpre[b,t,n]  +  skip_scale * gskip-term  +  gin_prev*[accumulate].
+ *   Pad adjoints: under SEL_PAD_ZERO taps outside [0, T) contribute nothing; under
+ *   SEL_PAD_REPLICATE the clamped taps add to the edge rows (the 2-tap transposed
+ *   form: row 0 also receives W[k=0]^T gpre[0]).  A gradient never crosses a
+ *   sample boundary.  act'(v) = 1 for v > 0, else act_slope (so act_slope at
+ *   v == 0, torch's convention); x may be NULL when act_slope is 1.
+ *   in_group_stride 0 (shared input): gin has C/G channels and is the sum over all
+ *   groups -- the adjoint of MultiGroupConv1d's repeat without a G-wide temporary.
+ *   gskip (may be NULL): the gradient arriving through a residual connection
+ *   that read the same x; it has pitch C and is added after the mask, times
+ *   skip_scale: gskip[m, g*C/G + c] with in_group_stride C/G, the sum over g of
+ *   those entries with in_group_stride 0.  The desc's accumulate adds the result to
+ *   the gin already there (the MultiReceptiveField blocks all feed one gx); its
+ *   res_group_stride and bias_period are not used.  `out` is read only with tanh_out.
+ *   Weights: wdpack = Wp with the outer and inner axis of each group block
+ *   exchanged, Wd[G][C/G][K][N/G] (same values, no rounding), so that the
+ *   reduction axis is contiguous.
+ *   bf16 contract: gout and W are bf16 operands as stored, products accumulate in
+ *   fp32, out_scale, mask, skip and accumulate are applied in fp32, gin is
+ *   rounded once.
+ *
+ * sel_hfg_conv_wgrad: gwpack[n][k][c] = sum_{b,t} gpre[b,t,n] * act(x[b, in_row(t + k*dil - pad), g*igs + c])
+ * in the packed layout Wp[N][K][C/G], always fp32 (sel_unpack_wgrad with
+ * SEL_PACK_FWD, cout = N, cin = C/G, or SEL_PACK_CONVT returns it to the torch
+ * layout); act(x) is rounded to bf16 once in the bf16 instance, as the forward
+ * does.  gbias (given exactly when bias_period > 0) [j] = sum of gpre[., n] over all n = j (mod
+ * bias_period): the transposed form sums its s output phases.  The rows are
+ * split over 64-row tiles into fixed-order partials in ws
+ * (sel_hfg_conv_wgrad_workspace bytes) with a fixed-order finish: no float
+ * atomics, two runs are bit-identical.  sel_tune key 72 > 0 forces the split
+ * count (clamped to the number of row tiles).
+ *
+ * sel_hfg_conv_bwd_kernel: the instance a shape takes.  wgrad 0, the data
+ * gradient: 0 = one thread per gin element (fp32, the tanh conv, C/G or N/G <= 4,
+ * tiles that do not fit LDS), 1 / 2 / 4 = the bf16 matrix-core tile of 64 rows x
+ * 16 / 32 / 64 channels.  wgrad 1: 0 = one thread per weight element and split,
+ * 1 = the bf16 matrix-core kernel.  Negative: bad descriptor. */
+int sel_hfg_conv_bwd_kernel(const sel_hfg_conv_desc* d, int in_dtype, int out_dtype, int wgrad);
+int sel_hfg_conv_bwd_data(const sel_hfg_conv_desc* d, int in_dtype, int out_dtype, const void* gout, const void* out,
+                          const void* x, const void* wdpack, const void* gskip, float skip_scale, void* gin,
+                          sel_stream_t stream);
+size_t sel_hfg_conv_wgrad_workspace(const sel_hfg_conv_desc* d, int in_dtype, int out_dtype);
+int sel_hfg_conv_wgrad(const sel_hfg_conv_desc* d, int in_dtype, int out_dtype, const void* gout, const void* out,
+                       const void* x, float* gwpack, float* gbias, void* ws, size_t ws_bytes, sel_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,13 @@
   residual layers (sel_tune key 71 = 1), and per (C/G, K) the fused residual
   layer (key 71 = 2) against two launches.
 
+* --train: generator forward + backward of VOCODER_V1 in bf16 at B = 16 x 32
+  latent frames (the recipes' batch_length 9600) through the training path
+  (Generator.enable_training): (forward + backward) against the training
+  forward alone, alternated in the same call, and per kernel instance the
+  time, algorithmic bytes / flops from the launches' metadata and the share
+  of its roof.  Writes profiles/vocoder_train_bench.json.
+
 All timing is by device events after warm-up, over windows of at least 0.5 s
 (whole model) / 0.2 s (single layers).  Writes JSON (default
 profiles/vocoder_bench.json).
@@ -166,13 +173,81 @@ def layer_ab(dev, B, gen):
     return rows
 
 
+TRAIN_CALLS = {"sel_hfg_conv_fwd", "sel_hfg_conv_bwd_data", "sel_hfg_conv_wgrad", "sel_pack_weight",
+               "sel_unpack_wgrad"}
+
+
+def train_bench(a):
+    """generator forward + backward through the training path, bf16"""
+    from models.vocoder.HiFiGAN import Generator
+    dev = torch.device("cuda:0")
+    gen = torch.Generator().manual_seed(0)
+    G = Generator(**configs.VOCODER_V1)
+    redraw(G, gen)
+    G = G.to(dev).train().enable_training()
+    batch, frames = a.batch, a.frames if a.frames != 160 else 32
+    x = torch.randn(batch, 64, frames, generator=gen).to(dev)
+    r = torch.randn(batch, 1, 300 * frames, generator=gen).to(dev)
+    res = dict(run=dict(tool="tools/vocoder_bench.py --train", date=time.strftime("%Y-%m-%d"),
+                        device=torch.cuda.get_device_name(0), config="VOCODER_V1", dtype="bf16", batch=batch,
+                        frames=frames, samples_per_clip=300 * frames))
+
+    def fwd():
+        return G(x)
+
+    def fwd_bwd():
+        G.zero_grad(set_to_none=True)
+        G(x).backward(r)
+
+    with CO.precision(torch.bfloat16):
+        mean, runs = ab({"forward_backward": fwd_bwd, "training_forward": fwd}, 1.5)
+        with torch.no_grad():
+            inf = event_loop(with_key(1, lambda: G(x)), 0.5)[0]
+        res["step_ms"] = dict(forward_backward=round(mean["forward_backward"], 4),
+                              training_forward=round(mean["training_forward"], 4),
+                              ratio=round(mean["forward_backward"] / mean["training_forward"], 3),
+                              no_grad_forward_two_launch=round(inf, 4), runs=runs)
+        print("step", res["step_ms"], flush=True)
+        # per kernel instance: one timed pass through the kernel timer (events around every call)
+        fwd_bwd()
+        timer = L.KernelTimer(TRAIN_CALLS)
+        L.TIMER = timer
+        try:
+            fwd_bwd()
+        finally:
+            L.TIMER = None
+        rows = []
+        ridge = BF16_PEAK / HBM_PEAK
+        for tag, (n, ms, nbytes, flops) in timer.summary().items():
+            t_roof = max(flops / BF16_PEAK, nbytes / HBM_PEAK) * 1e3
+            rows.append(dict(kernel=tag, launches=n, ms=round(ms, 4), gflop=round(flops / 1e9, 3),
+                             mbytes=round(nbytes / 1e6, 3), bound="bf16" if flops / max(nbytes, 1) > ridge else "hbm",
+                             roof_ms=round(t_roof, 4), share_of_roof=round(t_roof / ms, 4) if ms > 0 else None))
+        rows.sort(key=lambda row: -row["ms"])
+        res["kernels"] = rows
+        res["kernel_ms_total"] = round(sum(row["ms"] for row in rows), 4)
+        for row in rows:
+            print(row, flush=True)
+    out = a.out if a.out != DEFAULT_OUT else os.path.join(REPO, "profiles", "vocoder_train_bench.json")
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+    print("wrote", out)
+
+
+DEFAULT_OUT = os.path.join(REPO, "profiles", "vocoder_bench.json")
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "vocoder_bench.json"))
+    ap.add_argument("--out", default=DEFAULT_OUT)
     ap.add_argument("--batch", type=int, default=16)
     ap.add_argument("--frames", type=int, default=160)
     ap.add_argument("--skip-layers", action="store_true")
+    ap.add_argument("--train", action="store_true", help="training mode: generator forward + backward (frames default 32)")
     a = ap.parse_args()
+    if a.train:
+        return train_bench(a)
     from models.vocoder.HiFiGAN import StreamGenerator
     dev = torch.device("cuda:0")
     gen = torch.Generator().manual_seed(0)
