@@ -4,14 +4,30 @@ VectorQuantize (:19-104) and ResidualVQ (:107-161) keep their constructor
 arguments and buffers (``embed`` (dim, n_embed), ``cluster_size``,
 ``embed_avg``), so reference checkpoints load.  Eval-mode forward (the denoise
 trainer's, trainer/denoise.py:60) runs the fused all-stage HIP kernel
-(sel/vqops.py); training mode additionally applies the EMA codebook update
-(:74-80) on device after the same kernel's assignment.
+(sel/vqops.py); training mode runs the same kernel for the assignment and then
+the fused EMA codebook update (:74-80, csrc/vq_ema.hip) for all stages at once.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from sel.vqops import ResidualVQFn
+from sel.vqops import ResidualVQFn, rvq_ema_update
+
+
+def _train_forward(flatten, stack, layers):
+    """Training-mode forward of ``layers`` on ``stack`` (their codebooks before
+    the update, S, D, K): the eval-mode assignment -- every stage picks its code
+    with its own pre-update codebook, so out / losses / perplexities / gradient
+    are the all-stage kernel's -- then the EMA update (reference :74-80) of the
+    layers in training mode, which touches only the layers' own buffers."""
+    aux = {}
+    out, losses, ppls, idx = ResidualVQFn.apply(flatten, stack, layers[0].commitment, aux)
+    update = [l.training for l in layers]
+    rvq_ema_update(aux["x"], stack.detach(), idx, aux["counts"], layers, update)
+    for l, u in zip(layers, update):
+        if u:
+            l._codebook_epoch += 1
+    return out, losses, ppls
 
 
 class VectorQuantize(nn.Module):
@@ -50,29 +66,15 @@ class VectorQuantize(nn.Module):
     def codebook(self):
         return self.embed.transpose(0, 1)
 
-    def _ema(self, flatten, ind):
-        """vq_module.py:74-80 (training mode only)."""
-        with torch.no_grad():
-            onehot_sum = torch.bincount(ind, minlength=self.n_embed).to(flatten.dtype)
-            self.cluster_size.mul_(self.decay).add_(onehot_sum, alpha=1 - self.decay)
-            embed_sum = torch.zeros_like(self.embed_avg).index_add_(1, ind, flatten.t())
-            self.embed_avg.mul_(self.decay).add_(embed_sum, alpha=1 - self.decay)
-            n = self.cluster_size.sum()
-            cs = (self.cluster_size + self.eps) / (n + self.n_embed * self.eps) * n
-            self.embed.copy_(self.embed_avg / cs.unsqueeze(0))
-        self._codebook_epoch += 1
-
     def forward(self, input):
         flatten = input.reshape(-1, self.dim)
         if self.training:
-            # assignment uses the pre-update codebook (reference order :64-80)
-            out, loss, ppl, idx = ResidualVQFn.apply(flatten.detach(), self.embed.unsqueeze(0),
-                                                     self.commitment)
-            self._ema(flatten.detach().float(), idx[0])
-            q = out.view_as(input)
-            loss = F.mse_loss(q.detach(), input) * self.commitment
-            return input + (q - input).detach(), loss, ppl[0]
-        out, loss, ppl, _ = ResidualVQFn.apply(flatten, self.embed.unsqueeze(0), self.commitment)
+            # the one-stage case of ResidualVQ's training forward; the stack is
+            # a copy, because the update writes self.embed and the backward
+            # reads the codebook the assignment used
+            out, loss, ppl = _train_forward(flatten, self.embed.unsqueeze(0).clone(), [self])
+        else:
+            out, loss, ppl, _ = ResidualVQFn.apply(flatten, self.embed.unsqueeze(0), self.commitment)
         return out.view_as(input), loss[0], ppl[0]
 
     def forward_index(self, input):
@@ -91,7 +93,8 @@ class ResidualVQ(nn.Module):
     def _stacked(self):
         # the (S, D, K) codebook stack, rebuilt only when a codebook changed
         # (EMA update, load_state_dict, .to(): a bumped epoch, new storage or
-        # a bumped version; writes through .data or raw pointers must call
+        # a bumped version; writes through .data or raw pointers -- the replays
+        # of a captured training-mode forward among them -- must call
         # VectorQuantize.invalidate_codebook())
         embeds = [l.embed for l in self.layers]
         if any(e.requires_grad for e in embeds):
@@ -104,17 +107,14 @@ class ResidualVQ(nn.Module):
         return self._stack_cache
 
     def forward(self, x):
-        if any(l.training for l in self.layers):
-            out, residual, losses, ppls = 0.0, x, [], []
-            for layer in self.layers:
-                q, l_, p_ = layer(residual)
-                residual = residual - q
-                out = out + q
-                losses.append(l_)
-                ppls.append(p_)
-            return out, torch.stack(losses), torch.stack(ppls)
         flatten = x.reshape(-1, x.shape[-1])
-        out, losses, ppls, _ = ResidualVQFn.apply(flatten, self._stacked(), self.layers[0].commitment)
+        if any(l.training for l in self.layers):
+            # every step writes the codebooks, so the stack is rebuilt here
+            # rather than cached: inside a graph capture the restack is then part
+            # of the graph and a replay reads the codebooks the last replay wrote
+            out, losses, ppls = _train_forward(flatten, torch.stack([l.embed for l in self.layers]), self.layers)
+        else:
+            out, losses, ppls, _ = ResidualVQFn.apply(flatten, self._stacked(), self.layers[0].commitment)
         return out.view(x.shape), losses, ppls
 
     def forward_index(self, x, flatten_idx=False):

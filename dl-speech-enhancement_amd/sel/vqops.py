@@ -1,4 +1,6 @@
 """Autograd op over the residual-VQ kernel (layers/vq_module.py:61-88, :119-134)."""
+import ctypes
+
 import torch
 
 from . import _lib as L
@@ -8,7 +10,10 @@ class ResidualVQFn(torch.autograd.Function):
     """(x (N, D), embeds (S, D, K)) -> (out (N, D), losses (S,), ppls (S,), idx (S, N))."""
 
     @staticmethod
-    def forward(ctx, x, embeds, commitment):
+    def forward(ctx, x, embeds, commitment, aux=None):
+        """``aux`` (a dict, optional) receives what the training-mode codebook
+        update needs beside the four outputs: the contiguous fp32 ``x`` the kernel
+        read and the code histogram ``counts`` (S, K)."""
         L.need_device(x, embeds)
         x = x.contiguous().float()
         embeds = embeds.contiguous()
@@ -34,6 +39,9 @@ class ResidualVQFn(torch.autograd.Function):
         # launches per step)
         ctx.set_materialize_grads(False)
         ctx.counts = counts
+        ctx.has_aux = aux is not None
+        if aux is not None:
+            aux["x"], aux["counts"] = x, counts
         return out, loss, ppl, idx
 
     @staticmethod
@@ -46,4 +54,47 @@ class ResidualVQFn(torch.autograd.Function):
         gl = g_loss.contiguous() if g_loss is not None else None
         L.call("sel_rvq_bwd", L.ptr(x), N, D, L.ptr(embeds[0]), K, L.ptr(idx[0]), L.ptr(go), L.ptr(gl),
                ctx.commitment, L.ptr(gx), L.stream())
-        return gx, None, None
+        return (gx, None, None, None) if ctx.has_aux else (gx, None, None)
+
+
+class _EmaStage(ctypes.Structure):
+    """sel_rvq_ema_stage (include/sel.h)"""
+    _fields_ = [("embed", ctypes.c_void_p), ("cluster_size", ctypes.c_void_p), ("embed_avg", ctypes.c_void_p),
+                ("update", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+@torch.no_grad()
+def rvq_ema_update(x, stack, idx, counts, layers, update=None):
+    """The EMA codebook update of every training-mode layer (vq_module.py:74-80)
+    after one ResidualVQFn forward, in one C call: x (N, D) fp32 and the stack
+    (S, D, K) are what the forward read, idx / counts what it wrote.  ``layers``
+    own the buffers (one per layer: they are state_dict entries); ``update[s]``
+    (default: ``layers[s].training``) selects the stages written.  The stack is
+    left untouched: the backward reads it."""
+    L.need_device(x, stack, idx, counts)
+    S, D, K = stack.shape
+    N = x.shape[0]
+    if len(layers) != S or x.shape[1] != D or tuple(idx.shape) != (S, N) or tuple(counts.shape) != (S, K):
+        raise L.SelError(f"rvq_ema_update: shapes disagree (x {tuple(x.shape)}, stack {tuple(stack.shape)}, "
+                         f"idx {tuple(idx.shape)}, counts {tuple(counts.shape)}, {len(layers)} layers)")
+    if not (x.is_contiguous() and stack.is_contiguous() and idx.is_contiguous() and counts.is_contiguous()
+            and x.dtype == torch.float32 and stack.dtype == torch.float32):
+        raise L.SelError("rvq_ema_update: needs the forward's own contiguous fp32 tensors")
+    update = [l.training for l in layers] if update is None else list(update)
+    decay, eps = layers[0].decay, layers[0].eps
+    tab = (_EmaStage * S)()
+    for s, (l, u) in enumerate(zip(layers, update)):
+        if (l.decay, l.eps) != (decay, eps):
+            raise L.SelError("rvq_ema_update: the layers' decay / eps differ")
+        for b in (l.embed, l.cluster_size, l.embed_avg):
+            L.need_device(b)
+            if not (b.is_contiguous() and b.dtype == torch.float32):
+                raise L.SelError("rvq_ema_update: codebook buffers must be contiguous fp32")
+        if (tuple(l.embed.shape) != (D, K) or tuple(l.embed_avg.shape) != (D, K)
+                or tuple(l.cluster_size.shape) != (K,) or l.embed.data_ptr() == stack[s].data_ptr()):
+            raise L.SelError("rvq_ema_update: a layer's embed / embed_avg must be (D, K), its cluster_size (K), "
+                             "and embed must not alias the stack")
+        tab[s] = _EmaStage(l.embed.data_ptr(), l.cluster_size.data_ptr(), l.embed_avg.data_ptr(), int(bool(u)), 0)
+    ws = L.workspace(L.lib().sel_rvq_ema_workspace(N, D, S, K), x.device)
+    L.call("sel_rvq_ema_update", L.ptr(x), N, D, L.ptr(stack), S, K, L.ptr(idx), L.ptr(counts),
+           ctypes.cast(tab, ctypes.c_void_p), float(decay), float(eps), L.ptr(ws), ws.numel(), L.stream())

@@ -297,6 +297,48 @@ int sel_rvq_bwd(const float* x, int64_t N, int D, const float* embed0, int K, co
                 const float* g_out, const float* g_loss, float commitment, float* g_x,
                 sel_stream_t stream);
 
+/* ---- residual VQ, training mode: the EMA codebook update, vq_module.py:74-80 ----
+ * Runs after sel_rvq_fwd on the same x / embeds / idx / counts.  Training mode
+ * changes nothing about the assignment (every stage picks its code with its own
+ * pre-update codebook), so this call is only the update, for all stages at once.
+ *
+ * Contract:
+ *   r_0 = x, r_{s+1} = r_s - (r_s + (e_s[idx_s] - r_s)): the forward's three fp32
+ *   operations in that order, so the residuals are the bits the forward used.
+ *   sum_s[d][k] = sum over {n : idx[s,n] = k} of r_s[n][d], in fp32, rows added in
+ *   ascending n: the order is fixed by idx alone.  No float atomics; two calls
+ *   on the same inputs give the same bits.
+ *   For each stage with update != 0 (omd = 1 - decay in fp32):
+ *     cluster_size <- cluster_size*decay + counts*omd
+ *     n  = sum_k cluster_size   (fixed-order reduction accumulated in double)
+ *     cs = (cluster_size + eps) / (n + K*eps) * n
+ *     embed_avg <- embed_avg*decay + sum*omd
+ *     embed <- embed_avg / cs
+ *   A code with no rows decays like any other (the same formula, zero sum).
+ *   Stages with update == 0 are in eval mode: their three buffers are not written.
+ * `embeds` (S, D, K) is the stack the forward read; it is read-only here (the
+ * backward reads it after the update) and must not alias any stage's `embed`.
+ * `counts` (S, K) must be the histogram of `idx` (S, N), as sel_rvq_fwd leaves it.
+ * The per-stage table is in HOST memory and is copied into the kernel arguments
+ * (as sel_pack_many_host's jobs): the modules keep one buffer per layer.
+ * The call enqueues on `stream`, makes no host synchronisation and no allocation,
+ * and can be captured into a graph.  Arguments are validated before any device
+ * work: N >= 1 (N == 0 is refused, as sel_rvq_finish refuses it), 0 < D <= 256,
+ * 0 < S <= 16, K > 0 (SEL_ERR_ARG); ws_bytes >= sel_rvq_ema_workspace
+ * (SEL_ERR_WORKSPACE); non-null pointers (SEL_ERR_ARG). */
+typedef struct sel_rvq_ema_stage {   /* one per stage, host memory, copied into the kernel arguments */
+  float* embed;         /* (D, K) in/out  */
+  float* cluster_size;  /* (K)    in/out  */
+  float* embed_avg;     /* (D, K) in/out  */
+  int32_t update;       /* 0: stage is in eval mode, its three buffers are not written */
+  int32_t reserved;
+} sel_rvq_ema_stage;
+size_t sel_rvq_ema_workspace(int64_t N, int D, int S, int K);
+int sel_rvq_ema_update(const float* x, int64_t N, int D, const float* embeds /* (S,D,K): the stack the forward read */,
+                       int S, int K, const int64_t* idx /* (S,N) */, const int32_t* counts /* (S,K) */,
+                       const sel_rvq_ema_stage* stages, float decay, float eps,
+                       void* ws, size_t ws_bytes, sel_stream_t stream);
+
 /* ---- data glue: dataloader/data_utils.py:12-22 (add_noise) ---------------
  * out = (exp(snr/10) * ||noise||_2 / ||speech||_2 * speech + noise) / 2 with
  * BATCH-GLOBAL norms over all n elements (math.exp, not 10^x, as the reference). */
