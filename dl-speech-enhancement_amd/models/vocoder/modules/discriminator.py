@@ -1,5 +1,6 @@
-"""HiFi-GAN discriminators — drop-in for the reference
-``models/vocoder/modules/discriminator.py`` (:26-447).
+"""HiFi-GAN and UnivNet discriminators — drop-in for the reference
+``models/vocoder/modules/discriminator.py`` (:26-447 HiFi-GAN, :450-638 UnivNet;
+the UnivNet spectral chains run on sel/sconvops.SpecChainFn).
 
 Same classes, constructor arguments, sub-module names and ``state_dict`` keys:
 the parameters live in torch ``Conv1d`` / ``Conv2d`` modules built exactly as in
@@ -24,6 +25,7 @@ from torch.nn.utils.spectral_norm import SpectralNorm
 
 from sel import convops as CO
 from sel import dconvops as DC
+from sel import sconvops as SC
 
 
 def _slope(name, params):
@@ -308,6 +310,104 @@ class HiFiGANScaleDiscriminator(nn.Module):
 
     def apply_spectral_norm(self):
         pass  # reference :364-372 matches Conv2d only
+
+
+class UnivNetSpectralDiscriminator(nn.Module):
+    """UnivNet spectral discriminator module (discriminator.py:450-580).
+
+    The parameters live in the reference's ``layers`` (five ``Sequential(Conv2d,
+    LeakyReLU)`` and a final ``Conv2d``, weight-normalised), never called:
+    ``forward`` is |STFT| (sel.sconvops.spectrogram) and one SpecChainFn over the
+    channels-last 2-D conv kernels.  Reference quirk kept: it returns the last
+    layer's tensor (B, 1, H', W') only, not a list."""
+
+    def __init__(self, fft_size, hop_size, win_length, window="hann_window",
+                 kernel_sizes=[(3, 9), (3, 9), (3, 9), (3, 9), (3, 3), (3, 3)],
+                 strides=[(1, 1), (1, 2), (1, 2), (1, 2), (1, 1), (1, 1)], channels=32, bias=True,
+                 nonlinear_activation="LeakyReLU", nonlinear_activation_params={"negative_slope": 0.2},
+                 use_weight_norm=True):
+        super().__init__()
+        self.fft_size = fft_size
+        self.hop_size = hop_size
+        self.win_length = win_length
+        self.register_buffer("window", getattr(torch, window)(win_length))
+        self.slope = _slope(nonlinear_activation, nonlinear_activation_params)
+        self.layers = nn.ModuleList()
+        assert len(kernel_sizes) == len(strides)
+        n = len(kernel_sizes)
+        self._specs = []
+        for i in range(n - 1):
+            in_chs = 1 if i == 0 else channels
+            self.layers += [nn.Sequential(
+                nn.Conv2d(in_chs, channels, kernel_sizes[i], stride=strides[i], bias=bias),
+                getattr(nn, nonlinear_activation)(**nonlinear_activation_params))]
+            self._specs.append((in_chs, channels, _pair(kernel_sizes[i]), _pair(strides[i]), True))
+        self.layers += [nn.Conv2d(channels, 1, kernel_size=kernel_sizes[-1], stride=strides[-1], bias=bias)]
+        self._specs.append((channels, 1, _pair(kernel_sizes[-1]), _pair(strides[-1]), False))
+        if not use_weight_norm:
+            raise NotImplementedError("the HIP spectral discriminator is weight-normalised (use_weight_norm=True)")
+        self.apply_weight_norm()
+        # the kernels' limits hold for the constructor arguments (include/sel.h)
+        self._plan = [SC.LayerSpec(*s) for s in self._specs]
+
+    def _convs(self):
+        return [l[0] if isinstance(l, nn.Sequential) else l for l in self.layers]
+
+    def _params(self):
+        out = []
+        for m in self._convs():
+            out += [m.weight_v, m.weight_g, m.bias]
+        return out
+
+    def plan(self):
+        return self._plan
+
+    def geometry(self, T):
+        """[(H, W)] of the spectrogram and every layer's output for T samples."""
+        return SC.geometry(T, self.fft_size, self.hop_size, self.win_length, self._plan)
+
+    def forward(self, x):
+        """x (B, 1, T) -> the last layer's output (B, 1, H', W') (:549-570)."""
+        b, c, t = x.shape
+        if c != 1:
+            raise NotImplementedError("the HIP spectral discriminator takes 1-channel input")
+        self.geometry(t)
+        mag = SC.spectrogram(x.reshape(b, t).float(), self.fft_size, self.hop_size, self.win_length, self.window)
+        return SC.SpecChainFn.apply(mag, self._plan, self.slope, CO.compute_dtype(),
+                                    getattr(self, "_frozen", False), *self._params())
+
+    def apply_weight_norm(self):
+        def _apply_weight_norm(m):
+            if isinstance(m, nn.Conv2d):
+                nn.utils.weight_norm(m)
+                logging.debug(f"Weight norm is applied to {m}.")
+        self.apply(_apply_weight_norm)
+
+
+def _pair(v):
+    return (int(v), int(v)) if isinstance(v, int) else (int(v[0]), int(v[1]))
+
+
+class UnivNetMultiResolutionSpectralDiscriminator(nn.Module):
+    """UnivNet multi-resolution spectral discriminator module (discriminator.py:583-638)."""
+
+    def __init__(self, fft_sizes=[1024, 2048, 512], hop_sizes=[120, 240, 50], win_lengths=[600, 1200, 240],
+                 window="hann_window",
+                 discriminator_params={"channels": 32,
+                                       "kernel_sizes": [(3, 9), (3, 9), (3, 9), (3, 9), (3, 3), (3, 3)],
+                                       "strides": [(1, 1), (1, 2), (1, 2), (1, 2), (1, 1), (1, 1)], "bias": True,
+                                       "nonlinear_activation": "LeakyReLU",
+                                       "nonlinear_activation_params": {"negative_slope": 0.2}}):
+        super().__init__()
+        assert len(fft_sizes) == len(hop_sizes) == len(win_lengths)
+        self.discriminators = nn.ModuleList()
+        for i in range(len(fft_sizes)):
+            params = copy.deepcopy(discriminator_params)
+            self.discriminators += [UnivNetSpectralDiscriminator(fft_size=fft_sizes[i], hop_size=hop_sizes[i],
+                                                                 win_length=win_lengths[i], window=window, **params)]
+
+    def forward(self, x):
+        return [f(x) for f in self.discriminators]
 
 
 class HiFiGANMultiScaleDiscriminator(nn.Module):

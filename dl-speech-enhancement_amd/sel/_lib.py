@@ -114,6 +114,11 @@ SIGNATURES = {
     "sel_hfg_conv_bwd_data": (I32, [P, I32, I32, P, P, P, P, P, F32, P, P]),
     "sel_hfg_conv_wgrad_workspace": (SZ, [P, I32, I32]),
     "sel_hfg_conv_wgrad": (I32, [P, I32, I32, P, P, P, P, P, P, SZ, P]),
+    "sel_sconv_check": (I32, [P]),
+    "sel_sconv_fwd": (I32, [P, I32, P, P, P, P, P]),
+    "sel_sconv_bwd_data": (I32, [P, I32, P, P, P, P, P]),
+    "sel_sconv_wgrad_workspace": (SZ, [P, I32]),
+    "sel_sconv_wgrad": (I32, [P, I32, P, P, P, P, P, SZ, P]),
 }
 
 _lock = threading.Lock()

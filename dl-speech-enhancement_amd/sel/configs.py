@@ -124,9 +124,44 @@ VOCODER_V0 = dict(_VOCODER, resblock_kernel_sizes=[3, 7, 11], resblock_dilations
 VOCODER_V1 = dict(_VOCODER, resblock_kernel_sizes=[11], resblock_dilations=[[1, 3, 5]], groups=3)
 VOCODER_V2 = dict(_VOCODER, resblock_kernel_sizes=[3], resblock_dilations=[[1, 3, 5]], groups=3)
 
+# UnivNet MRSD + MPD discriminator (config/autoencoder/symADuniv_vctk_48000_hop300.yaml:47-85)
+UNIV_DISCRIMINATOR = dict(
+    fft_sizes=[1024, 2048, 512], hop_sizes=[120, 240, 50], win_lengths=[600, 1200, 240], window="hann_window",
+    spectral_discriminator_params=dict(channels=32, kernel_sizes=[[3, 9], [3, 9], [3, 9], [3, 9], [3, 3], [3, 3]],
+                                       strides=[[1, 1], [1, 2], [1, 2], [1, 2], [1, 1], [1, 1]], bias=True,
+                                       nonlinear_activation="LeakyReLU",
+                                       nonlinear_activation_params=dict(negative_slope=0.2)),
+    periods=[2, 3, 5, 7, 11],
+    period_discriminator_params=DISCRIMINATOR["period_discriminator_params"])
+
+# the stage-1 recipe with the UnivNet discriminator (model_type symAudioDecUniv,
+# config/autoencoder/symADuniv_vctk_48000_hop300.yaml): trainer/autoencoder.py's key set
+SYMADUNIV_VCTK_48K = dict(
+    sampling_rate=48000, model_type="symAudioDecUniv", train_mode="autoencoder", paradigm="efficient",
+    generator_params=GENERATOR, discriminator_params=UNIV_DISCRIMINATOR, **ADV,
+    use_mel_loss=True,
+    mel_loss_params=dict(fs=48000, fft_sizes=[2048], hop_sizes=[300], win_lengths=[2048], window="hann_window",
+                         num_mels=80, fmin=0, fmax=24000, log_base=None),
+    use_stft_loss=False, stft_loss_params=STFT, use_shape_loss=False, shape_loss_params=dict(winlen=[300]),
+    lambda_adv=1.0, lambda_feat_match=2.0, lambda_vq_loss=1.0, lambda_mel_loss=45.0, lambda_stft_loss=45.0,
+    lambda_shape_loss=45.0,
+    batch_size=16, batch_length=9600, adv_batch_length=9600,
+    generator_optimizer_type="Adam", generator_optimizer_params=dict(lr=1.0e-4, betas=[0.5, 0.9], weight_decay=0.0),
+    generator_scheduler_type="StepLR", generator_scheduler_params=dict(step_size=200000, gamma=1.0),
+    generator_grad_norm=-1,
+    discriminator_optimizer_type="Adam",
+    discriminator_optimizer_params=dict(lr=2.0e-4, betas=[0.5, 0.9], weight_decay=0.0),
+    discriminator_scheduler_type="MultiStepLR",
+    discriminator_scheduler_params=dict(gamma=0.5, milestones=[200000, 400000, 600000, 800000]),
+    discriminator_grad_norm=-1,
+    start_steps=dict(generator=0, discriminator=500000), train_max_steps=500000, adv_train_max_steps=1000000,
+    save_interval_steps=100000, eval_interval_steps=1000, log_interval_steps=100,
+)
+
 CONFIGS = {"symAD_libritts_24000_hop300": SYMAD_LIBRITTS_24K_DENOISE, "symAD_24Mel": SYMAD_24MEL,
            "symAD_24MelNDO": SYMAD_24MEL_NDO, "symAD_24MelNDOSNR": SYMAD_24MEL_NDOSNR,
-           "symAD_custom": SYMAD_CUSTOM, "symAD_vctk_48000_hop300": SYMAD_VCTK_48K_GAN}
+           "symAD_custom": SYMAD_CUSTOM, "symAD_vctk_48000_hop300": SYMAD_VCTK_48K_GAN,
+           "symADuniv_vctk_48000_hop300": SYMADUNIV_VCTK_48K}
 
 
 def get(name):

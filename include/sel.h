@@ -665,6 +665,58 @@ size_t sel_hfg_conv_wgrad_workspace(const sel_hfg_conv_desc* d, int in_dtype, in
 int sel_hfg_conv_wgrad(const sel_hfg_conv_desc* d, int in_dtype, int out_dtype, const void* gout, const void* out,
                        const void* x, float* gwpack, float* gbias, void* ws, size_t ws_bytes, sel_stream_t stream);
 
+/* ---- UnivNet spectral discriminator: channels-last 2-D conv ---------------
+ * models/vocoder/modules/discriminator.py:450-580 (UnivNetSpectralDiscriminator):
+ * Conv2d(Cin, Cout, (kh, kw), stride (sh, sw)), valid padding, over
+ * x (B, H, W, Cin) rows (H frames, W frequency bins) ->
+ * y (B, H - kh + 1, (W - kw) / sw + 1, Cout), then LeakyReLU(slope) when act.
+ *
+ * Limits (anything else returns SEL_ERR_ARG naming the limit, before any device
+ * work): kh <= 3, kw <= 9, sh = 1, sw in {1, 2}, kw >= sw; channels 1 -> C,
+ * C -> C' or C -> 1 with C, C' multiples of 32, at most 256.
+ *
+ * Element types: `dtype` (SEL_F32 / SEL_BF16) is the type of every activation
+ * with C > 1 channels; the 1-channel tensors (the magnitudes entering a 1 -> C
+ * layer and their gradient, the output of a C -> 1 layer and its gradient) are
+ * always fp32.  Products accumulate in fp32.
+ *
+ * Packed weights (written by the caller from the effective weight
+ * w (Cout, Cin, kh, kw), sel/sconvops.py):
+ *   forward  C -> C':  fp32: wpack[kh][kw][Cout][Cin]; bf16: wpack[2][kh][kw][Cout][Cin],
+ *            the bf16 rounding of w and then the bf16 rounding of its remainder
+ *            w - bf16(w) (two bf16 matrix products per tap, so the pre-activations
+ *            -- and with them the LeakyReLU masks the backward reuses -- carry the
+ *            rounding of the stored activations only);
+ *            1 -> C and C -> 1:  wpack[kh][kw][C] fp32.
+ *   adjoint: for each input-column phase p < sw, the taps kw = p (mod sw)
+ *            flipped on both axes, Kp = ceil((kw - p) / sw) of them per row,
+ *            phases concatenated:  C -> C': [kh][Kp][Cin][Cout] in `dtype`;
+ *            1 -> C and C -> 1: [kh][Kp][C] fp32.
+ *
+ * sel_sconv_bwd_data: gx = adjoint(gy) (a gather per phase, no atomics), times
+ * LeakyReLU'(aux) when aux (the stored output of the previous layer, i.e. this
+ * layer's input, same layout as gx) is given.  Input columns no tap reads get
+ * an exact 0.
+ * sel_sconv_wgrad: gw (Cout, Cin, kh, kw) and gb (Cout; may be NULL), fp32, of
+ * the effective weight: per-block partials over contiguous ranges of output
+ * rows in ws (sel_sconv_wgrad_workspace bytes), then a fixed-order sum: no
+ * atomics, two runs give identical bits. */
+typedef struct sel_sconv_desc {
+  int32_t B, H, W;      /* input rows (frames) and columns (bins) */
+  int32_t Cin, Cout;
+  int32_t kh, kw, sh, sw;
+  int32_t act;          /* forward: LeakyReLU(slope) after the bias */
+  float slope;
+} sel_sconv_desc;
+int sel_sconv_check(const sel_sconv_desc* d); /* the limits above; no device work */
+int sel_sconv_fwd(const sel_sconv_desc* d, int dtype, const void* x, const void* wpack, const float* bias, void* y,
+                  sel_stream_t stream);
+int sel_sconv_bwd_data(const sel_sconv_desc* d, int dtype, const void* gy, const void* wadj, const void* aux,
+                       void* gx, sel_stream_t stream);
+size_t sel_sconv_wgrad_workspace(const sel_sconv_desc* d, int dtype);
+int sel_sconv_wgrad(const sel_sconv_desc* d, int dtype, const void* gy, const void* x, float* gw, float* gb, void* ws,
+                    size_t ws_bytes, sel_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
