@@ -6,24 +6,44 @@ arguments and buffers (``embed`` (dim, n_embed), ``cluster_size``,
 trainer's, trainer/denoise.py:60) runs the fused all-stage HIP kernel
 (sel/vqops.py); training mode runs the same kernel for the assignment and then
 the fused EMA codebook update (:74-80, csrc/vq_ema.hip) for all stages at once.
+
+Data parallel, ``enable_ema_sync`` (switched on by ``sel.dist.sync_vq``) replaces
+the fused update by its two halves (csrc/vq_ema_sync.hip): per-code statistics of
+this rank's rows, gathered from all ranks in rank order, then applied -- so every
+rank's codebooks follow the rows of the whole batch and stay bit-identical.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from sel.vqops import ResidualVQFn, rvq_ema_update
+from sel.dist import gather_blocks
+from sel.vqops import ResidualVQFn, rvq_ema_apply, rvq_ema_stats, rvq_ema_update
 
 
-def _train_forward(flatten, stack, layers):
+def _train_forward(flatten, stack, layers, sync=None):
     """Training-mode forward of ``layers`` on ``stack`` (their codebooks before
     the update, S, D, K): the eval-mode assignment -- every stage picks its code
     with its own pre-update codebook, so out / losses / perplexities / gradient
     are the all-stage kernel's -- then the EMA update (reference :74-80) of the
-    layers in training mode, which touches only the layers' own buffers."""
+    layers in training mode, which touches only the layers' own buffers.
+
+    ``sync`` = (process group or None, segments or None), set by
+    ``enable_ema_sync``: the update in two halves.  The statistics of this
+    process's rows, one block per segment, are gathered from every rank of the
+    group in rank order and applied block by block, so the codebooks follow the
+    global batch and are the same bits on every rank.  out / idx / losses /
+    perplexities / gradient are untouched (they come from the pre-update stack);
+    the perplexities stay rank-local, computed from this rank's rows."""
     aux = {}
     out, losses, ppls, idx = ResidualVQFn.apply(flatten, stack, layers[0].commitment, aux)
     update = [l.training for l in layers]
-    rvq_ema_update(aux["x"], stack.detach(), idx, aux["counts"], layers, update)
+    if sync is None:
+        rvq_ema_update(aux["x"], stack.detach(), idx, aux["counts"], layers, update)
+    else:
+        group, segments = sync
+        stats = rvq_ema_stats(aux["x"], stack.detach(), idx, segments or 1)
+        blocks = gather_blocks(stats, group)            # (W, nseg, S, D + 1, K), rank-major
+        rvq_ema_apply(blocks.view(-1, *stats.shape[1:]), layers, update)
     for l, u in zip(layers, update):
         if u:
             l._codebook_epoch += 1
@@ -50,9 +70,20 @@ class VectorQuantize(nn.Module):
         # A write that bypasses both (.data / raw device pointers) must call
         # invalidate_codebook().
         self._codebook_epoch = 0
+        self._ema_sync = None  # (process group, segments) once enable_ema_sync was called
 
     def invalidate_codebook(self):
         self._codebook_epoch += 1
+
+    def enable_ema_sync(self, process_group=None, segments=None):
+        """Update the codebook from the rows of every rank of ``process_group``
+        (None: the default group, if one is initialised) instead of this rank's
+        alone; see ``ResidualVQ.enable_ema_sync``.  Opt-in; not part of the
+        state_dict."""
+        self._ema_sync = (process_group, segments)
+
+    def disable_ema_sync(self):
+        self._ema_sync = None
 
     def _apply(self, fn, *args, **kwargs):
         self._codebook_epoch += 1
@@ -72,7 +103,7 @@ class VectorQuantize(nn.Module):
             # the one-stage case of ResidualVQ's training forward; the stack is
             # a copy, because the update writes self.embed and the backward
             # reads the codebook the assignment used
-            out, loss, ppl = _train_forward(flatten, self.embed.unsqueeze(0).clone(), [self])
+            out, loss, ppl = _train_forward(flatten, self.embed.unsqueeze(0).clone(), [self], self._ema_sync)
         else:
             out, loss, ppl, _ = ResidualVQFn.apply(flatten, self.embed.unsqueeze(0), self.commitment)
         return out.view_as(input), loss[0], ppl[0]
@@ -89,6 +120,24 @@ class ResidualVQ(nn.Module):
     def __init__(self, *, num_quantizers, **kwargs):
         super().__init__()
         self.layers = nn.ModuleList([VectorQuantize(**kwargs) for _ in range(num_quantizers)])
+        self._ema_sync = None
+
+    def enable_ema_sync(self, process_group=None, segments=None):
+        """Data-parallel EMA update (opt-in; ``sel.dist.sync_vq`` calls it after
+        broadcasting the buffers): each training forward computes the per-code
+        statistics of its own rows in ``segments or 1`` equal row segments
+        (sel.vqops.rvq_ema_stats), gathers every rank's blocks in rank order
+        (sel.dist.gather_blocks) and applies them left to right
+        (rvq_ema_apply).  The codebooks then follow the global batch and are
+        bit-identical on all ranks, for any world size and collective algorithm.
+        ``segments=W`` without a process group is the simulated data-parallel
+        mode: one process on the concatenated batch of W equal shards produces
+        the bits that W ranks produce.  The perplexities stay rank-local.  Nothing
+        is added to the state_dict."""
+        self._ema_sync = (process_group, segments)
+
+    def disable_ema_sync(self):
+        self._ema_sync = None
 
     def _stacked(self):
         # the (S, D, K) codebook stack, rebuilt only when a codebook changed
@@ -112,7 +161,8 @@ class ResidualVQ(nn.Module):
             # every step writes the codebooks, so the stack is rebuilt here
             # rather than cached: inside a graph capture the restack is then part
             # of the graph and a replay reads the codebooks the last replay wrote
-            out, losses, ppls = _train_forward(flatten, torch.stack([l.embed for l in self.layers]), self.layers)
+            out, losses, ppls = _train_forward(flatten, torch.stack([l.embed for l in self.layers]), self.layers,
+                                               self._ema_sync)
         else:
             out, losses, ppls, _ = ResidualVQFn.apply(flatten, self._stacked(), self.layers[0].commitment)
         return out.view(x.shape), losses, ppls

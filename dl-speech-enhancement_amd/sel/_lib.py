@@ -69,6 +69,10 @@ SIGNATURES = {
     "sel_rvq_bwd": (I32, [P, I64, I32, P, I32, P, P, P, F32, P, P]),
     "sel_rvq_ema_workspace": (SZ, [I64, I32, I32, I32]),
     "sel_rvq_ema_update": (I32, [P, I64, I32, P, I32, I32, P, P, P, F32, F32, P, SZ, P]),
+    "sel_rvq_ema_stats_floats": (SZ, [I32, I32, I32]),
+    "sel_rvq_ema_stats_workspace": (SZ, [I64, I32, I32, I32]),
+    "sel_rvq_ema_stats": (I32, [P, I64, I32, P, I32, I32, P, I32, P, P, SZ, P]),
+    "sel_rvq_ema_apply": (I32, [P, I32, I32, I32, I32, P, F32, F32, P]),
     "sel_add_noise_workspace": (SZ, [I64]),
     "sel_add_noise": (I32, [P, P, I64, F32, P, P, SZ, P]),
     "sel_power_mel_fwd": (I32, [P, I64, I64, I32, I32, I32, P, P, P, I32, F32, P, P]),

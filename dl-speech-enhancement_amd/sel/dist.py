@@ -12,6 +12,10 @@ reference quantities are *batch-global* and need an explicit exchange:
     the whole batch -> all-reduce the per-rank partial sums (sum (y-x)^2,
     sum y^2, sum |ln y - ln x|, element count) before the ratio
     (global_loss_sums; used by sel/spectral.py's STFT-loss autograd ops).
+Stage 1 (trainer/autoencoder.py) has a third: the residual VQ's codebooks are
+buffers updated from the rows a rank sees (layers/vq_module.py:74-80), which
+gradient averaging never reaches -> broadcast once, then per-code statistics
+gathered in rank order before every update (sync_vq, gather_blocks).
 """
 import os
 
@@ -117,6 +121,51 @@ def add_noise_global(speech, noise, snr):
     b = noise.contiguous().float()
     sums = allreduce_sum_(_local_sumsq(a, b))
     return _mix(a, b, sums, snr)
+
+
+def gather_blocks(t, process_group=None):
+    """Every rank's ``t`` (same shape and dtype on all ranks) as one tensor
+    (W, *t.shape), in rank order, on every rank; without a process group (or
+    torch.distributed not initialised) ``t`` itself with a leading 1.  The
+    blocks are gathered, not reduced: what a caller then computes from them in
+    block order is the same on every rank whatever the collective's algorithm.
+    ``dist.all_gather`` into views of one buffer: gloo and RCCL both take that
+    form (``all_gather_into_tensor`` is not on every backend)."""
+    if not is_dist():
+        return t.unsqueeze(0)
+    world = dist.get_world_size(process_group)
+    if world == 1:
+        return t.unsqueeze(0)
+    t = t.contiguous()
+    out = torch.empty((world,) + tuple(t.shape), dtype=t.dtype, device=t.device)
+    dist.all_gather(list(out.unbind(0)), t, group=process_group)
+    return out
+
+
+def sync_vq(module, process_group=None):
+    """Keep the vector quantizers under ``module`` in step across the ranks:
+    every VectorQuantize's ``embed`` / ``cluster_size`` / ``embed_avg`` is
+    broadcast from the group's rank 0 (the buffers come from each rank's own
+    ``torch.randn`` stream, and SelDDP broadcasts parameters only) and its cached
+    stack invalidated; then the EMA statistics exchange is switched on for every
+    ResidualVQ / VectorQuantize (``enable_ema_sync``), so that each training
+    forward updates the codebooks from all ranks' rows.  Returns the number of
+    codebooks touched; does nothing (0) without a process group or with one rank."""
+    from layers.vq_module import ResidualVQ, VectorQuantize
+    if not is_dist() or dist.get_world_size(process_group) == 1:
+        return 0
+    src = dist.get_global_rank(process_group, 0) if process_group is not None else 0
+    touched = 0
+    for m in module.modules():
+        if isinstance(m, VectorQuantize):
+            with torch.no_grad():
+                for b in (m.embed, m.cluster_size, m.embed_avg):
+                    dist.broadcast(b.data, src=src, group=process_group)
+            m.invalidate_codebook()
+            touched += 1
+        if isinstance(m, (ResidualVQ, VectorQuantize)):
+            m.enable_ema_sync(process_group=process_group)
+    return touched
 
 
 DDP_BUCKET_MB = float(os.environ.get("SEL_DDP_BUCKET_MB", "4"))

@@ -98,3 +98,62 @@ def rvq_ema_update(x, stack, idx, counts, layers, update=None):
     ws = L.workspace(L.lib().sel_rvq_ema_workspace(N, D, S, K), x.device)
     L.call("sel_rvq_ema_update", L.ptr(x), N, D, L.ptr(stack), S, K, L.ptr(idx), L.ptr(counts),
            ctypes.cast(tab, ctypes.c_void_p), float(decay), float(eps), L.ptr(ws), ws.numel(), L.stream())
+
+
+@torch.no_grad()
+def rvq_ema_stats(x, stack, idx, nseg=1):
+    """The statistics of the EMA codebook update (vq_module.py:74-80) on their
+    own, after one ResidualVQFn forward: (nseg, S, D + 1, K) fp32, block g
+    holding, per stage, the per-code sums of the residual rows of segment g (rows
+    [g N / nseg, (g + 1) N / nseg), planes 0..D-1) and their counts (plane D).
+    Every element is written.  ``rvq_ema_apply`` folds such blocks -- this
+    process's, or all ranks' gathered in rank order -- into the codebooks."""
+    L.need_device(x, stack, idx)
+    S, D, K = stack.shape
+    N = x.shape[0]
+    if x.dim() != 2 or x.shape[1] != D or tuple(idx.shape) != (S, N):
+        raise L.SelError(f"rvq_ema_stats: shapes disagree (x {tuple(x.shape)}, stack {tuple(stack.shape)}, "
+                         f"idx {tuple(idx.shape)})")
+    if not (x.is_contiguous() and stack.is_contiguous() and idx.is_contiguous() and x.dtype == torch.float32
+            and stack.dtype == torch.float32 and idx.dtype == torch.int64):
+        raise L.SelError("rvq_ema_stats: needs the forward's own contiguous fp32 tensors and int64 indices")
+    nseg = int(nseg)
+    stats = torch.empty((max(nseg, 0), S, D + 1, K), dtype=torch.float32, device=x.device)
+    ws = L.workspace(L.lib().sel_rvq_ema_stats_workspace(N, D, S, K), x.device)
+    L.call("sel_rvq_ema_stats", L.ptr(x), N, D, L.ptr(stack), S, K, L.ptr(idx), nseg, L.ptr(stats), L.ptr(ws),
+           ws.numel(), L.stream())
+    return stats
+
+
+@torch.no_grad()
+def rvq_ema_apply(stats, layers, update=None):
+    """Fold ``stats`` (nblk, S, D + 1, K) -- blocks of ``rvq_ema_stats``, summed
+    left to right in block order -- into the buffers of ``layers`` (one per
+    stage); ``update[s]`` (default: ``layers[s].training``) selects the stages
+    written.  One block from one segment gives the bits of ``rvq_ema_update``."""
+    L.need_device(stats)
+    if stats.dim() != 4 or len(layers) != stats.shape[1]:
+        raise L.SelError(f"rvq_ema_apply: stats {tuple(stats.shape)} is not (nblk, S, D + 1, K) for "
+                         f"{len(layers)} layers")
+    nblk, S, D1, K = stats.shape
+    D = D1 - 1
+    if not (stats.is_contiguous() and stats.dtype == torch.float32):
+        raise L.SelError("rvq_ema_apply: stats must be contiguous fp32")
+    update = [l.training for l in layers] if update is None else list(update)
+    if len(update) != S:
+        raise L.SelError("rvq_ema_apply: one update flag per layer")
+    decay, eps = layers[0].decay, layers[0].eps
+    tab = (_EmaStage * S)()
+    for s, (l, u) in enumerate(zip(layers, update)):
+        if (l.decay, l.eps) != (decay, eps):
+            raise L.SelError("rvq_ema_apply: the layers' decay / eps differ")
+        for b in (l.embed, l.cluster_size, l.embed_avg):
+            L.need_device(b)
+            if not (b.is_contiguous() and b.dtype == torch.float32):
+                raise L.SelError("rvq_ema_apply: codebook buffers must be contiguous fp32")
+        if (tuple(l.embed.shape) != (D, K) or tuple(l.embed_avg.shape) != (D, K)
+                or tuple(l.cluster_size.shape) != (K,)):
+            raise L.SelError("rvq_ema_apply: a layer's embed / embed_avg must be (D, K), its cluster_size (K)")
+        tab[s] = _EmaStage(l.embed.data_ptr(), l.cluster_size.data_ptr(), l.embed_avg.data_ptr(), int(bool(u)), 0)
+    L.call("sel_rvq_ema_apply", L.ptr(stats), nblk, D, S, K, ctypes.cast(tab, ctypes.c_void_p), float(decay),
+           float(eps), L.stream())

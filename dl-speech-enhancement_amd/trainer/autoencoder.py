@@ -11,11 +11,18 @@ generator adds the adversarial and feature-matching losses; under the
 frozen at that point and the codebooks are kept in eval mode, so only the
 decoder goes on learning.  The discriminator step recomputes the prediction
 under no_grad from the updated generator (:117-126).
+
+Under a process group (torch.distributed.run, the models wrapped by
+sel.dist.wrap_ddp) the codebooks are buffers that gradient averaging does not
+reach: the constructor calls sel.dist.sync_vq, which broadcasts them from rank 0
+and makes every EMA update use the statistics of all ranks' rows, so the
+replicas stay bit-identical and the checkpoint holds the global batch's codebook.
 """
 import logging
 
 import torch
 
+from sel import dist as seldist
 from trainer.trainerGAN import TrainerVQGAN
 
 
@@ -29,9 +36,16 @@ class Trainer(TrainerVQGAN):
         start = config.get("start_steps", {})
         self.generator_start = start.get("generator", 0)
         self.discriminator_start = start.get("discriminator", 200000)
+        if seldist.is_dist():  # (sync_vq does nothing with one rank)
+            seldist.sync_vq(self._gen())
+
+    def _gen(self):
+        """The generator's own module (a data-parallel wrapper keeps it as .module)."""
+        gen = self.model["generator"]
+        return getattr(gen, "module", gen)
 
     def _freeze_encoder_side(self):
-        gen = self.model["generator"]
+        gen = self._gen()
         for part in (gen.encoder, gen.projector, gen.quantizer):
             for p in part.parameters():
                 p.requires_grad = False
@@ -48,7 +62,7 @@ class Trainer(TrainerVQGAN):
         if self.discriminator_train and not self.fix_encoder and self.paradigm == "efficient":
             self._freeze_encoder_side()
         if self.fix_encoder:
-            gen.quantizer.codebook.eval()  # no EMA update once the encoder side is fixed
+            self._gen().quantizer.codebook.eval()  # no EMA update once the encoder side is fixed
 
         # generator: commitment + metric (+ adversarial + feature matching)
         if self.generator_train:

@@ -339,6 +339,58 @@ int sel_rvq_ema_update(const float* x, int64_t N, int D, const float* embeds /* 
                        const sel_rvq_ema_stage* stages, float decay, float eps,
                        void* ws, size_t ws_bytes, sel_stream_t stream);
 
+/* ---- the same update in two halves, for data-parallel training: vq_module.py:74-80 ----
+ * sel_rvq_ema_update folds each code's sum straight into embed_avg, so its
+ * statistics never exist on their own.  This pair stops in between: the stats
+ * call leaves the per-code sums and counts of this rank's rows in a buffer the
+ * ranks exchange (sel.dist.gather_blocks: gathered in rank order, not
+ * all-reduced), the apply call folds the gathered blocks into the codebooks.
+ * sel_rvq_ema_update itself is unchanged.
+ *
+ * Contract of sel_rvq_ema_stats (after sel_rvq_fwd on the same x / embeds / idx):
+ *   r_s as above: the forward's three fp32 operations in its order.
+ *   Segment g (0 <= g < nseg) is the rows [g*N/nseg, (g+1)*N/nseg).
+ *   stats is (nseg, S, D+1, K) fp32, sel_rvq_ema_stats_floats(D,S,K) = S*(D+1)*K
+ *   floats per block.  Block g, stage s:
+ *     planes 0..D-1: sum[d][k] = sum over {n in segment g : idx[s,n] = k} of
+ *                    r_s[n][d], in fp32 from 0, rows added in ascending n;
+ *     plane D:       the number of those rows, as fp32 (exact: a segment has at
+ *                    most 2^24 rows).
+ *   EVERY element of stats is written, codes without rows included (zeros): the
+ *   caller need not clear it.  No float atomics; two calls on the same inputs
+ *   give the same bits.
+ *   Validated before any device work: the shape limits of sel_rvq_ema_update;
+ *   1 <= nseg <= 65535, N % nseg == 0, N/nseg <= 2^24 (SEL_ERR_ARG);
+ *   ws_bytes >= sel_rvq_ema_stats_workspace (SEL_ERR_WORKSPACE); non-null
+ *   pointers (SEL_ERR_ARG).
+ *
+ * Contract of sel_rvq_ema_apply on stats (nblk, S, D+1, K), nblk >= 1 blocks of
+ * that layout (nblk = ranks x segments per rank, in rank-major order).  For each
+ * stage with update != 0 (omd = 1 - decay in fp32):
+ *     sum = ((blk_0 + blk_1) + blk_2) + ...       fp32, left to right in block order
+ *     cnt = blk_0 + blk_1 + ...                   the count plane, in double,
+ *                                                 converted to float once
+ *     embed_avg    <- fmaf(sum, omd, embed_avg*decay)
+ *     cluster_size <- fmaf(float(cnt), omd, cluster_size*decay)
+ *     n, cs, embed as in sel_rvq_ema_update (the same fixed fp64 tree for n).
+ *   Stages with update == 0 are not written.  The result depends on the blocks
+ *   and their order alone, so every rank that applies the same gathered blocks
+ *   to equal codebooks keeps equal codebooks, for any number of ranks, whatever
+ *   the collective's algorithm.  With nseg = nblk = 1 the pair writes the bits
+ *   of sel_rvq_ema_update.
+ *   The stage table is in HOST memory, as above.  Validated before any device
+ *   work: 0 < D <= 256, 0 < S <= 16, K > 0, nblk >= 1, non-null stats / table,
+ *   non-null buffers in every stage with update != 0 (all SEL_ERR_ARG).
+ * Both calls enqueue on `stream`, make no host synchronisation and no
+ * allocation, and can be captured into a graph. */
+size_t sel_rvq_ema_stats_floats(int D, int S, int K);
+size_t sel_rvq_ema_stats_workspace(int64_t N, int D, int S, int K);
+int sel_rvq_ema_stats(const float* x, int64_t N, int D, const float* embeds /* (S,D,K): the stack the forward read */,
+                      int S, int K, const int64_t* idx /* (S,N) */, int nseg,
+                      float* stats /* (nseg, S, D+1, K) */, void* ws, size_t ws_bytes, sel_stream_t stream);
+int sel_rvq_ema_apply(const float* stats /* (nblk, S, D+1, K) */, int nblk, int D, int S, int K,
+                      const sel_rvq_ema_stage* stages, float decay, float eps, sel_stream_t stream);
+
 /* ---- data glue: dataloader/data_utils.py:12-22 (add_noise) ---------------
  * out = (exp(snr/10) * ||noise||_2 / ||speech||_2 * speech + noise) / 2 with
  * BATCH-GLOBAL norms over all n elements (math.exp, not 10^x, as the reference). */

@@ -17,6 +17,18 @@ alike).  Writes JSON (default profiles/vq_train_bench.json).
 
   python tools/vq_train_bench.py [--out PATH]
 
+``--sync`` measures the data-parallel codebook update instead (csrc/vq_ema_sync.hip,
+``ResidualVQ.enable_ema_sync``), in one process and without a process group:
+
+* ``fused``  as above;
+* ``sync1``  statistics + apply with one segment (what each rank of a process
+  group runs on its own rows, without the gather);
+* ``sync8``  statistics in 8 segments + apply of the 8 blocks (what the apply
+  costs on the gathered blocks of 8 ranks; the statistics of one rank's 1/8).
+
+Same alternation, events and windows; also records the bytes a step gathers,
+W x S x (D + 1) x K x 4.  Writes profiles/vq_sync_bench.json by default.
+
 ``--trace VARIANT --rows N`` runs 3 + 10 calls of one variant and nothing else:
 for a kernel trace from outside (launches per call = kernel calls / 13).
 """
@@ -87,16 +99,23 @@ def event_loop(fn, min_seconds, max_iters=100000):
     return e0.elapsed_time(e1) / n, n
 
 
-def variants(n, dev):
+SYNC_SEGMENTS = {"sync1": 1, "sync8": 8}
+
+
+def variants(n, dev, sync=False):
     gen = torch.Generator().manual_seed(n)
     torch.manual_seed(0)
     base = ResidualVQ(num_quantizers=S, dim=D, codebook_size=K)
     x = (1.5 * torch.randn(n, D, generator=gen)).to(dev)
     mods = {}
-    for name in ("fused", "torch"):
+    for name in ("fused",) + (tuple(SYNC_SEGMENTS) if sync else ("torch",)):
         m = ResidualVQ(num_quantizers=S, dim=D, codebook_size=K)
         m.load_state_dict(base.state_dict())
+        if name in SYNC_SEGMENTS:
+            m.enable_ema_sync(segments=SYNC_SEGMENTS[name])
         mods[name] = m.to(dev).train()
+    if sync:
+        return {name: (lambda m=m: m(x)) for name, m in mods.items()}
     return {"fused": lambda: mods["fused"](x), "torch": lambda: torch_forward(mods["torch"], x)}
 
 
@@ -109,14 +128,18 @@ def no_grad(fn):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "vq_train_bench.json"))
-    ap.add_argument("--trace", choices=("fused", "torch"))
+    ap.add_argument("--out")
+    ap.add_argument("--sync", action="store_true", help="fused against statistics + apply (1 and 8 segments)")
+    ap.add_argument("--trace", choices=("fused", "torch") + tuple(SYNC_SEGMENTS))
     ap.add_argument("--rows", type=int, default=512)
     ap.add_argument("--seconds", type=float, default=0.5)
     a = ap.parse_args()
+    a.sync = a.sync or a.trace in SYNC_SEGMENTS
+    if a.out is None:
+        a.out = os.path.join(REPO, "profiles", "vq_sync_bench.json" if a.sync else "vq_train_bench.json")
     dev = torch.device("cuda:0")
     if a.trace:
-        fn = no_grad(variants(a.rows, dev)[a.trace])
+        fn = no_grad(variants(a.rows, dev, a.sync)[a.trace])
         for _ in range(13):
             fn()
         torch.cuda.synchronize()
@@ -125,16 +148,22 @@ def main():
     res = dict(run=dict(tool="tools/vq_train_bench.py", date=time.strftime("%Y-%m-%d"),
                         device=torch.cuda.get_device_name(0), stages=S, codes=K, dim=D,
                         window_seconds=a.seconds), rows={})
+    if a.sync:
+        res["run"]["gathered_bytes_per_step"] = {f"W={w}": w * S * (D + 1) * K * 4 for w in (1, 2, 8)}
     for n in ROWS:
-        fns = {k: no_grad(f) for k, f in variants(n, dev).items()}
+        fns = {k: no_grad(f) for k, f in variants(n, dev, a.sync).items()}
         acc = {k: [] for k in fns}
         for _ in range(3):                       # alternated, round by round
             for k, fn in fns.items():
                 acc[k].append(event_loop(fn, a.seconds)[0])
         mean = {k: sum(v) / len(v) for k, v in acc.items()}
-        res["rows"][str(n)] = dict(fused_ms=round(mean["fused"], 4), torch_ms=round(mean["torch"], 4),
-                                   speedup=round(mean["torch"] / mean["fused"], 2),
-                                   runs={k: [round(t, 4) for t in v] for k, v in acc.items()})
+        if a.sync:
+            row = {f"{k}_ms": round(v, 4) for k, v in mean.items()}
+            row.update({f"{k}_over_fused": round(mean[k] / mean["fused"], 3) for k in SYNC_SEGMENTS})
+        else:
+            row = dict(fused_ms=round(mean["fused"], 4), torch_ms=round(mean["torch"], 4),
+                       speedup=round(mean["torch"] / mean["fused"], 2))
+        res["rows"][str(n)] = dict(row, runs={k: [round(t, 4) for t in v] for k, v in acc.items()})
         print(n, res["rows"][str(n)], flush=True)
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
