@@ -12,66 +12,14 @@ from its fp64 run (e32, stored in the golden), the bound is 3 x that e32, read
 from the golden — never from this code's output."""
 import copy
 
-import numpy as np
 import pytest
 import torch
-import torch.nn.functional as F
 
 import univnet_ref as U
 from conftest import golden
+from sconv_cases import LAYER_CASES, SLOPE, _cl, layer_ref, rel
 
 pytestmark = pytest.mark.gpu
-
-TILE = 64  # output columns per block of the matrix-core kernels (sconv2d.hip BM)
-
-# (B, H, W, Cin, Cout, kernel, stride)
-LAYER_CASES = {
-    "s2_odd_tail": (3, 4, 40, 32, 32, (3, 9), (1, 2)),    # W - kw odd: the last input column is read by no tap
-    "s1": (3, 4, 40, 32, 32, (3, 9), (1, 1)),
-    "one_row": (2, 3, 11, 32, 32, (3, 3), (1, 1)),        # one output row, fewer columns than a tile
-    "tile_plus": (2, 5, 2 * (TILE + 13 - 1) + 9, 32, 32, (3, 9), (1, 2)),  # output width TILE + 13
-    "first": (3, 5, 21, 1, 32, (3, 9), (1, 1)),
-    "last": (3, 4, 13, 32, 1, (3, 3), (1, 1)),
-    "c64": (2, 4, 24, 64, 64, (3, 9), (1, 2)),
-}
-SLOPE = 0.2
-
-
-def rel(a, b):
-    a = a.detach().double().cpu()
-    b = torch.as_tensor(np.asarray(b)).double() if not torch.is_tensor(b) else b.detach().double().cpu()
-    return ((a - b).norm() / b.norm().clamp_min(1e-30)).item()
-
-
-def _cl(t):
-    """(B, C, H, W) -> channels-last rows (B, H, W, C)"""
-    return t.permute(0, 2, 3, 1).contiguous()
-
-
-_REF = {}
-
-
-def _layer_ref(name):
-    """fp64 CPU reference of one case, computed once and shared by both precisions."""
-    if name in _REF:
-        return _REF[name]
-    B, H, W, ci, co, k, s = LAYER_CASES[name]
-    g = torch.Generator().manual_seed(sum(map(ord, name)))
-    leaky = co != 1
-    u = torch.randn(B, ci, H, W, generator=g)
-    x = F.leaky_relu(u, SLOPE) if ci != 1 else u.abs()        # a stored LeakyReLU output / magnitudes
-    w = torch.randn(co, ci, *k, generator=g) / (ci * k[0] * k[1]) ** 0.5
-    b = 0.1 * torch.randn(co, generator=g)
-    xd = x.double().requires_grad_(True)
-    wd = w.double().requires_grad_(True)
-    bd = b.double().requires_grad_(True)
-    z = F.conv2d(xd, wd, bd, stride=s)
-    gpre = torch.randn(z.shape, generator=g)
-    (z * gpre.double()).sum().backward()
-    gx = xd.grad * torch.where(x > 0, 1.0, SLOPE).double() if ci != 1 else xd.grad
-    y = F.leaky_relu(z, SLOPE) if leaky else z
-    _REF[name] = dict(x=x, w=w, b=b, gpre=gpre, y=y.detach(), gx=gx, gw=wd.grad, gb=bd.grad, leaky=leaky)
-    return _REF[name]
 
 
 @pytest.mark.parametrize("dtype", ["fp32", "bf16"])
@@ -79,7 +27,7 @@ def _layer_ref(name):
 def test_layer_kernels_match_conv2d(gpu, name, dtype):
     from sel import sconvops as SC
     B, H, W, ci, co, k, s = LAYER_CASES[name]
-    r = _layer_ref(name)
+    r = layer_ref(name, LAYER_CASES[name])
     dt = torch.float32 if dtype == "fp32" else torch.bfloat16
     tol_f, tol_g = (1e-5, 1e-4) if dtype == "fp32" else (1e-2, 2e-2)
     sp = SC.LayerSpec(ci, co, k, s, r["leaky"])
