@@ -99,6 +99,12 @@ class StreamGenerator(Generator):
     def decode(self, zq):
         return self.decoder.decode(zq.transpose(2, 1))
 
+    def session(self, batch=1, chunk=300, graph=True):
+        """An opt-in sel.streaming.StreamSession over this generator: fixed state,
+        one step launch per layer, each hop replayed as a graph."""
+        from sel.streaming import StreamSession
+        return StreamSession(self, batch, chunk, graph)
+
     def reset_buffer(self):
         """Zero every causal layer's pad_buffer (AudioDec.py:185-191)."""
         from layers.conv_layer import CausalConv1d, CausalConvTranspose1d

@@ -57,3 +57,4 @@ class StreamGenerator(Generator):
         return self.decoder.decode(zq)
 
     reset_buffer = _PQCStream.reset_buffer
+    session = _PQCStream.session

@@ -123,6 +123,8 @@ SIGNATURES = {
     "sel_sconv_bwd_data": (I32, [P, I32, P, P, P, P, P]),
     "sel_sconv_wgrad_workspace": (SZ, [P, I32]),
     "sel_sconv_wgrad": (I32, [P, I32, P, P, P, P, P, SZ, P]),
+    "sel_conv_step": (I32, [P, I32, I32, P, P, P, P, P, P, P, P]),
+    "sel_stream_commit": (I32, [P, I32, P]),
 }
 
 _lock = threading.Lock()

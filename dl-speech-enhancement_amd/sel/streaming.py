@@ -1,0 +1,213 @@
+"""Streaming codec sessions: a hop as a fixed list of step launches, replayed
+as a HIP graph.
+
+``StreamGenerator.encode/decode`` (models/autoencoder*/AudioDec.py) run every
+causal layer through ``*.inference``: a ``cat`` with the pad_buffer, a fresh
+buffer tensor per call, the training conv kernel, a slice.  A ``StreamSession``
+runs the same hop as one ``sel_conv_step`` launch per layer (csrc/stream.hip)
+plus one ``sel_stream_commit``, on buffers allocated once: every activation,
+every carry (the pad_buffers, channels-last) and their ``carry_out`` twins live
+at fixed addresses, so ``encode`` and ``decode`` are each captured into one
+graph (single stream, no parallel branches) and replayed per hop.
+
+The session is opt-in and changes nothing on the module path; the two exchange
+state through ``load_state`` / ``store_state``.
+"""
+import torch
+
+from . import _lib as L
+from . import convops as CO
+from . import streamops as SO
+
+
+class _Half:
+    """The launches of one method (encode or decode) on fixed buffers."""
+
+    def __init__(self, steps, generator, batch, in_channels, dtype, device):
+        params = dict(generator.named_parameters())
+        self.steps = steps
+        self.batch = batch
+        T0 = steps[0].T * (steps[0].stride if steps[0].kind == CO.PACK_FWD_STRIDED else 1)
+        self.inp = torch.zeros((batch, T0, in_channels), dtype=dtype, device=device)
+        self.descs, self.wps, self.biases, self.outs = [], [], [], []
+        self.carry, self.carry_out = [], []
+        for st in steps:
+            w = params[st.weight]
+            L.need_device(w)
+            self.descs.append(st.desc(batch))
+            self.wps.append(CO.PACKS.get(st.kind, w, st.stride, dtype)[0])
+            self.biases.append(params[st.bias].detach().float().contiguous() if st.bias else None)
+            self.outs.append(torch.zeros((batch * st.T, st.N), dtype=torch.float32 if st.out_float else dtype,
+                                         device=device))
+            if st.carry_shape is None:
+                self.carry.append(None)
+                self.carry_out.append(None)
+            else:
+                self.carry.append(torch.zeros(st.carry_shape, dtype=dtype, device=device))
+                self.carry_out.append(torch.zeros(st.carry_shape, dtype=dtype, device=device))
+        self.pairs = [(o, c) for o, c in zip(self.carry_out, self.carry) if c is not None]
+        self.graph = None
+
+    def _buf(self, i):
+        return self.inp if i == -1 else self.outs[i]
+
+    def launch(self):
+        for i, st in enumerate(self.steps):
+            SO.conv_step(self.descs[i], self.carry[i], self._buf(st.src), self.wps[i], self.biases[i],
+                         None if st.res is None else self._buf(st.res), self.outs[i], self.carry_out[i])
+        SO.commit(self.pairs)
+
+    def capture(self, warmup=2):
+        dev = self.inp.device
+        # eager warm-up on a side stream, as trainer/graph.py does it
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            for _ in range(warmup):
+                self.launch()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self.launch()
+
+    def run(self):
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self.launch()
+        return self.outs[-1]
+
+    def zero(self):
+        for c in self.carry:
+            if c is not None:
+                c.zero_()
+
+
+class StreamSession:
+    """One streaming endpoint state: ``batch`` parallel streams, ``chunk`` samples per hop.
+
+    ``encode(x) -> z``, ``quantize(z) -> idx``, ``lookup(idx) -> zq`` and
+    ``decode(zq) -> y`` take and return what the ``StreamGenerator`` methods do
+    (shapes and dtypes; for ``batch > 1`` ``lookup`` returns (batch, frames, dim),
+    the layout ``decode`` takes).
+
+    The tensors ``encode`` and ``decode`` return are VIEWS of the session's fixed
+    output buffers: they are valid until the next call of the same method, which
+    overwrites them in place (clone what must outlive it).  Inputs are copied
+    into fixed input buffers, so the caller's tensors are free after the call.
+
+    State: every causal layer's carry starts at zero (``reset()``);
+    ``load_state()`` copies the generator's pad_buffers in -- so the reference's
+    warm-up, ``G.initial_encoder(...)`` / ``G.initial_decoder(...)`` on the module
+    path followed by ``load_state()``, is the supported one, and
+    ``receptive_length`` need not be a multiple of ``chunk`` -- and
+    ``store_state()`` writes the carries back as pad_buffers in the reference's
+    shapes.  The packed weights are those of the pack cache when the session is
+    built; build a new session after the weights change.
+
+    ``graph=True``: ``encode`` and ``decode`` are each one captured graph on a
+    single stream (warm-up on a side stream, then capture); ``graph=False``
+    issues the same launches eagerly.  Both produce the same bits.
+    ``dtype=None`` follows ``sel.convops.compute_dtype()``.
+    """
+
+    def __init__(self, generator, batch=1, chunk=300, graph=True, dtype=None):
+        self.generator = generator
+        # whose codebooks quantize / lookup use (a receiver decodes with one
+        # generator and looks codes up in its copy of the encoder's: utils/audiodec.py)
+        self.lookup_generator = generator
+        self.plan = SO.plan(generator, batch, chunk)
+        self.dtype = dtype or CO.compute_dtype()
+        p = next(generator.parameters())
+        L.need_device(p)
+        L.lib()
+        dev = p.device
+        pl = self.plan
+        with torch.no_grad():
+            self._enc = _Half(pl.encode, generator, batch, pl.in_channels, self.dtype, dev)
+            self._dec = _Half(pl.decode, generator, batch, pl.dec_in_channels, self.dtype, dev)
+            if hasattr(generator, "quantizer") and not hasattr(generator.quantizer.codebook, "codebook_size"):
+                generator.quantizer.initial()
+            self.graphed = bool(graph)
+            if graph:
+                self._enc.capture()
+                self._dec.capture()
+                self.reset()   # the warm-up hops ran on zero input; start from zero state
+
+    # ---- the four methods of the reference's streamer -------------------------
+    @torch.no_grad()
+    def encode(self, x):
+        """x (batch, in_channels, chunk) -> z (batch, code_dim, frames) fp32 (without
+        PQC: the encoder output in the compute dtype)."""
+        pl = self.plan
+        L.need_device(x)
+        if tuple(x.shape) != (pl.batch, pl.in_channels, pl.chunk):
+            raise L.SelError(f"sel: session encode takes {(pl.batch, pl.in_channels, pl.chunk)}, got {tuple(x.shape)}")
+        self._enc.inp.copy_(x.transpose(1, 2))
+        return self._enc.run().view(pl.batch, pl.frames, pl.enc_channels).transpose(1, 2)
+
+    @torch.no_grad()
+    def quantize(self, z):
+        """z -> flattened code indices (sel_rvq_fwd, as StreamGenerator.quantize)."""
+        return self.lookup_generator.quantize(z)
+
+    @torch.no_grad()
+    def lookup(self, idx):
+        zq = self.lookup_generator.lookup(idx)
+        return zq.reshape(self.plan.batch, self.plan.frames, zq.shape[-1])
+
+    @torch.no_grad()
+    def decode(self, zq):
+        """zq (batch, frames, code_dim) -- without PQC (batch, channels, frames) --
+        -> y (batch, out_channels, samples) fp32."""
+        pl = self.plan
+        L.need_device(zq)
+        src = zq if pl.pqc else zq.transpose(1, 2)
+        if tuple(src.shape) != (pl.batch, pl.frames, pl.dec_in_channels):
+            raise L.SelError(f"sel: session decode takes {pl.frames} frames of {pl.dec_in_channels} channels "
+                             f"for {pl.batch} streams, got {tuple(zq.shape)}")
+        self._dec.inp.copy_(src)
+        return self._dec.run().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
+
+    # ---- state ------------------------------------------------------------------
+    def _layers(self):
+        for half in (self._enc, self._dec):
+            for st, c in zip(half.steps, half.carry):
+                if c is not None:
+                    yield st, c, self.generator.get_submodule(st.name)
+
+    def carries(self):
+        """{pad_buffer key: carry tensor (batch, P, C), channels-last} -- the live state."""
+        return {st.buffer: c for st, c, _ in self._layers()}
+
+    @torch.no_grad()
+    def reset(self):
+        self._enc.zero()
+        self._dec.zero()
+
+    @torch.no_grad()
+    def load_state(self):
+        """carries <- the generator's pad_buffers ((1 or batch, C, P), broadcast to batch)."""
+        for st, c, m in self._layers():
+            pb = m.pad_buffer
+            if pb.shape[0] not in (1, c.shape[0]) or tuple(pb.shape[1:]) != tuple(st.buffer_shape[1:]):
+                raise L.SelError(f"sel: {st.buffer} has shape {tuple(pb.shape)}, the session holds "
+                                 f"{st.buffer_shape} per stream")
+            rows = pb.to(c.device).transpose(1, 2).expand(c.shape[0], -1, -1)      # (batch, P_ref, Cin)
+            if st.kind == CO.PACK_FWD_STRIDED:
+                # 2s samples as 2 phase rows; the extra oldest sample meets a zero weight
+                v = c.view(c.shape[0], 2 * st.stride, -1)
+                v[:, :1].zero_()
+                v[:, 1:].copy_(rows)
+            else:
+                c.copy_(rows)
+
+    @torch.no_grad()
+    def store_state(self):
+        """The generator's pad_buffers <- carries, in the reference's shapes (fp32)."""
+        for st, c, m in self._layers():
+            v = c.view(c.shape[0], -1, st.buffer_shape[1])
+            if st.kind == CO.PACK_FWD_STRIDED:
+                v = v[:, 1:]
+            m.pad_buffer = v.transpose(1, 2).float().contiguous()

@@ -277,6 +277,44 @@ int sel_conv_replicate_fix(const sel_conv_desc* d, int dtype, const void* gout,
 int sel_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n,
              sel_stream_t stream);
 
+/* ---- streaming step: layers/conv_layer.py:144-147 (CausalConv1d.inference),
+ * :185-188 (CausalConvTranspose1d.inference), residual_unit.py:78-81 ---------
+ * One causal layer of one streaming hop, on channels-last rows, with the
+ * reference's pad_buffer as an explicit carry.  Same descriptor as sel_conv_fwd:
+ *   T = d->T NEW rows per sample, B = d->rows / T, P = (K-1)*dil;
+ *   d->pad must equal P and pad_mode must be SEL_PAD_ZERO (SEL_ERR_ARG otherwise);
+ *   v[b] = [ carry[b] (P rows) | act(in[b]) (T rows) ], act = ELU when in_elu,
+ *          applied to the new rows only (the carry holds what pad_buffer holds:
+ *          for a residual unit's conv1 the ACTIVATED signal);
+ *   out[b,t,n] = sum_{k,c} Wp[n][k][c] * v[b, t + k*dil, c] + bias[n % bias_period] + res[b,t,n];
+ *   carry_out[b] = the last P rows of v[b], in in_dtype, copied bit for bit
+ *          (T < P keeps P - T rows of the old carry).  carry is never written;
+ *          carry_out must not alias carry (SEL_ERR_ARG).  K = 1: P = 0, carry and
+ *          carry_out may be NULL (the residual unit's 1x1 with its + x as res).
+ * Wp is what sel_pack_weight writes: SEL_PACK_FWD as is; SEL_PACK_FWD_STRIDED a
+ * 3-tap conv over the phase view (C = s*Cin, P = 2 phase rows = 2s samples, the
+ * oldest of which meets a structurally zero weight); SEL_PACK_CONVT a 2-tap conv
+ * with N = s*Cout and P = 1 (the previous input row where the training forward
+ * replicates), out viewed as (T*s, Cout) = deconv(cat(buf, x))[s:-s].
+ * in_dtype / out_dtype: fp32 -> fp32, bf16 -> bf16 or fp32; res has the output
+ * type.  Any C and N; C % 8 == 0 with 16-byte aligned pointers takes 16-byte
+ * operand loads.  The K*C reduction is split over the waves of a block by the
+ * layer shape alone and summed in wave order: no atomics, two calls give the
+ * same bits, and a sample's output does not depend on B or T.  No workspace.
+ * Arguments are validated before any device work. */
+int sel_conv_step(const sel_conv_desc* d, int in_dtype, int out_dtype, const void* carry, const void* in,
+                  const void* wpack, const float* bias, const void* res, void* out, void* carry_out,
+                  sel_stream_t stream);
+/* End of a hop: copy every layer's carry_out into its carry in one launch per
+ * 48 jobs (`jobs` is a HOST array, copied into the kernel arguments), so all
+ * streaming state lives at fixed addresses and a hop can be captured in a graph. */
+typedef struct sel_copy_job {
+  const void* src;
+  void* dst;
+  int64_t bytes;
+} sel_copy_job;
+int sel_stream_commit(const sel_copy_job* jobs, int njobs, sel_stream_t stream);
+
 /* ---- residual VQ: layers/vq_module.py:61-88 (eval), :119-134 -------------
  * All stages of one row block in one launch (rows are independent):
  *   dist_k = (|r|^2 - (2r).e_k) + |e_k|^2, idx = argmin (lowest index on ties),
