@@ -15,17 +15,14 @@
 //                T or the row-tile count
 //   carry_out  = written by extra blocks of the same launch (the last P rows of
 //                the virtual input, the same act() on the new rows)
-#include "conv_common.h"
+#include "step_common.h"
 
 #include <algorithm>
 
 namespace sel {
 namespace stream {
-using namespace sel::conv;
+using namespace sel::step;
 
-constexpr int MAX_NW = 8;     // waves per block (reduction split)
-constexpr int BIG_RT = 4;     // row tiles per block on large row counts
-constexpr int RT_SWITCH = 64; // row tiles (of 16 rows) from which a block takes BIG_RT of them
 constexpr int COMMIT_MAXJ = 48;
 
 struct StepArgs {
@@ -34,10 +31,6 @@ struct StepArgs {
   int KC, nchunk, ncol, ngrp;
   int64_t carry_elems;  // B * P * C
 };
-
-template <typename T> struct Frag;
-template <> struct Frag<__bf16> { typedef bf16x8 type; static constexpr int E = 8; };
-template <> struct Frag<float> { typedef floatx4 type; static constexpr int E = 4; };
 
 // the activation of the new rows: one function for the conv operand and for
 // carry_out, so the carried rows are the bits the conv consumed
@@ -106,17 +99,6 @@ __device__ __forceinline__ typename Frag<TI>::type load_b(const StepArgs& a, con
       if (r0 + i < a.KC) f[i] = row[r0 + i];
   }
   return f;
-}
-
-__device__ __forceinline__ floatx4 mma(bf16x8 a, bf16x8 b, floatx4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-}
-// four 16x16x4 products: product j takes element j of every lane's vector, i.e.
-// the reduction index 16*chunk + 4*(lane >> 4) + j on both operands
-__device__ __forceinline__ floatx4 mma(floatx4 a, floatx4 b, floatx4 c) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) c = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], c, 0, 0, 0);
-  return c;
 }
 
 template <typename TI, typename TO, bool VEC, int RT>

@@ -225,6 +225,12 @@ class StreamGenerator(Generator):
                              out_dtype=torch.float32)
         return x.transpose(1, 2)
 
+    def session(self, batch=1, frames=1, graph=True):
+        """An opt-in sel.streaming.VocoderSession over this generator: fixed state,
+        one grouped step launch per conv, each hop of `frames` frames replayed as a graph."""
+        from sel.streaming import VocoderSession
+        return VocoderSession(self, batch, frames, graph)
+
     def reset_buffer(self):
         """Zero every streaming pad_buffer."""
 

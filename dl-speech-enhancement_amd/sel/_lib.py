@@ -125,6 +125,7 @@ SIGNATURES = {
     "sel_sconv_wgrad": (I32, [P, I32, P, P, P, P, P, SZ, P]),
     "sel_conv_step": (I32, [P, I32, I32, P, P, P, P, P, P, P, P]),
     "sel_stream_commit": (I32, [P, I32, P]),
+    "sel_hfg_conv_step": (I32, [P, I32, I32, P, P, P, P, P, P, P, P]),
 }
 
 _lock = threading.Lock()

@@ -12,6 +12,12 @@ graph (single stream, no parallel branches) and replayed per hop.
 
 The session is opt-in and changes nothing on the module path; the two exchange
 state through ``load_state`` / ``store_state``.
+
+``VocoderSession`` is the same for the receiver of the shipped codecs, the
+HiFi-GAN vocoder ``StreamGenerator.decode`` (models/vocoder/HiFiGAN.py): one
+``sel_hfg_conv_step`` launch per conv (csrc/hfg_step.hip; groups, LeakyReLU,
+tanh and the MultiReceptiveField mean inside the kernel), one commit per 48
+carries, one graph.
 """
 import torch
 
@@ -211,3 +217,131 @@ class StreamSession:
             if st.kind == CO.PACK_FWD_STRIDED:
                 v = v[:, 1:]
             m.pad_buffer = v.transpose(1, 2).float().contiguous()
+
+
+class _VocoderHalf(_Half):
+    """The launches of a vocoder ``decode`` on fixed buffers (capture / run / zero as _Half)."""
+
+    def __init__(self, steps, generator, batch, in_channels, dtype, device):
+        from . import hfgops as HF
+        self.steps = steps
+        self.batch = batch
+        self.inp = torch.zeros((batch, steps[0].T, in_channels), dtype=dtype, device=device)
+        self.descs, self.wps, self.biases, self.outs = [], [], [], []
+        self.carry, self.carry_out = [], []
+        for i, st in enumerate(steps):
+            m = generator.get_submodule(st.conv)
+            self.descs.append(st.desc(batch))
+            self.wps.append(HF.packed(m, st.kind, st.stride, dtype))
+            self.biases.append(m.bias.detach().float().contiguous() if st.bias_period else None)
+            if st.out != i:
+                self.outs.append(self.outs[st.out])    # accumulates into an earlier step's buffer
+            else:
+                self.outs.append(torch.zeros((batch * st.T, st.N), dtype=torch.float32 if st.out_float else dtype,
+                                             device=device))
+            if st.carry_shape is None:
+                self.carry.append(None)
+                self.carry_out.append(None)
+            else:
+                self.carry.append(torch.zeros(st.carry_shape, dtype=dtype, device=device))
+                self.carry_out.append(torch.zeros(st.carry_shape, dtype=dtype, device=device))
+        self.pairs = [(o, c) for o, c in zip(self.carry_out, self.carry) if c is not None]
+        self.graph = None
+
+    def launch(self):
+        for i, st in enumerate(self.steps):
+            SO.hfg_conv_step(self.descs[i], self.carry[i], self._buf(st.src), self.wps[i], self.biases[i],
+                             None if st.res is None else self._buf(st.res), self.outs[i], self.carry_out[i])
+        SO.commit(self.pairs)
+
+
+class VocoderSession:
+    """The receiver's streaming state for a HiFi-GAN vocoder ``StreamGenerator``:
+    ``batch`` parallel streams, ``frames`` code frames per hop.
+
+    ``decode(c)`` takes what ``StreamGenerator.decode`` takes, (batch, frames,
+    in_channels), and returns (batch, out_channels, frames * prod(upsample_scales))
+    fp32 -- a VIEW of the session's fixed output buffer, valid until the next
+    ``decode`` (clone what must outlive it).  ``decode_norm`` (the generator's
+    ``stats``) is applied while the input buffer is filled, outside the graph.
+    ``lookup(idx)`` goes through ``lookup_generator`` (the receiver's copy of the
+    encoder, set by utils/audiodec.py) and returns (batch, frames, code_dim).
+
+    State as StreamSession: every carry starts at zero (``reset()``);
+    ``load_state()`` copies the generator's pad_buffers in (the reference's
+    warm-up, ``G.initial_decoder(...)`` on the module path, then ``load_state()``)
+    and ``store_state()`` writes the carries back as fp32 pad_buffers in the
+    reference's shapes.  The packed weights (weight norm folded) are those of
+    sel.hfgops' pack cache when the session is built; build a new session after
+    the weights change.
+
+    ``graph=True``: a hop is one captured graph on a single stream -- the three
+    independent MultiReceptiveField blocks of v0 are issued in order on it, no
+    side streams (warm-up on a side stream, then capture, then ``reset()``);
+    ``graph=False`` issues the same launches eagerly.  Both produce the same bits.
+    ``dtype=None`` follows ``sel.convops.compute_dtype()``.
+    """
+
+    def __init__(self, generator, batch=1, frames=1, graph=True, dtype=None):
+        self.generator = generator
+        self.lookup_generator = None
+        self.plan = SO.plan_vocoder(generator, batch, frames)
+        self.dtype = dtype or CO.compute_dtype()
+        p = next(generator.parameters())
+        L.need_device(p)
+        L.lib()
+        pl = self.plan
+        with torch.no_grad():
+            self._dec = _VocoderHalf(pl.steps, generator, batch, pl.in_channels, self.dtype, p.device)
+            self.graphed = bool(graph)
+            if graph:
+                self._dec.capture()
+                self.reset()   # the warm-up hops ran on zero input; start from zero state
+
+    @torch.no_grad()
+    def lookup(self, idx):
+        if self.lookup_generator is None:
+            raise L.SelError("sel: this VocoderSession has no lookup_generator (the generator whose codebooks "
+                             "decode the indices)")
+        zq = self.lookup_generator.lookup(idx)
+        return zq.reshape(self.plan.batch, self.plan.frames, zq.shape[-1])
+
+    @torch.no_grad()
+    def decode(self, c):
+        """c (batch, frames, in_channels) -> y (batch, out_channels, samples) fp32."""
+        pl = self.plan
+        L.need_device(c)
+        if tuple(c.shape) != (pl.batch, pl.frames, pl.in_channels):
+            raise L.SelError(f"sel: session decode takes {(pl.batch, pl.frames, pl.in_channels)}, got {tuple(c.shape)}")
+        self._dec.inp.copy_(self.generator.decode_norm(c))
+        return self._dec.run().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
+
+    # ---- state ------------------------------------------------------------------
+    def _layers(self):
+        for st, c in zip(self._dec.steps, self._dec.carry):
+            if c is not None:
+                yield st, c, self.generator.get_submodule(st.name)
+
+    def carries(self):
+        """{pad_buffer key: carry tensor (batch, P, C), channels-last} -- the live state."""
+        return {st.buffer: c for st, c, _ in self._layers()}
+
+    @torch.no_grad()
+    def reset(self):
+        self._dec.zero()
+
+    @torch.no_grad()
+    def load_state(self):
+        """carries <- the generator's pad_buffers ((1 or batch, C, P), broadcast to batch)."""
+        for st, c, m in self._layers():
+            pb = m.pad_buffer
+            if pb.shape[0] not in (1, c.shape[0]) or tuple(pb.shape[1:]) != tuple(st.buffer_shape[1:]):
+                raise L.SelError(f"sel: {st.buffer} has shape {tuple(pb.shape)}, the session holds "
+                                 f"{st.buffer_shape} per stream")
+            c.copy_(pb.to(c.device).transpose(1, 2).expand(c.shape[0], -1, -1))
+
+    @torch.no_grad()
+    def store_state(self):
+        """The generator's pad_buffers <- carries, in the reference's shapes (fp32)."""
+        for _, c, m in self._layers():
+            m.pad_buffer = c.transpose(1, 2).float().contiguous()

@@ -9,6 +9,11 @@ host -- no GPU, no libsel call -- and returns, for ``encode`` and for
 ``decode``, the ordered list of steps a hop consists of.  ``sel.streaming``
 turns a plan into fixed buffers and launches; tests/test_stream_plan_host.py
 executes one on the CPU against the oracle.
+
+``hfg_conv_step`` binds ``sel_hfg_conv_step`` (csrc/hfg_step.hip), the grouped
+LeakyReLU form of the same step, and ``plan_vocoder`` walks a HiFi-GAN vocoder
+``StreamGenerator`` (models/vocoder/HiFiGAN.py) the same way;
+tests/test_vocoder_plan_host.py executes its plans against the reference goldens.
 """
 import ctypes
 from dataclasses import dataclass
@@ -212,3 +217,215 @@ def plan(generator, batch, chunk):
 
     return Plan(batch, chunk, frames, pqc, generator.input_channels, e.steps[-1].N, d.steps[0].C,
                 d.steps[-1].N, T, tuple(e.steps), tuple(d.steps))
+
+
+# ---- the HiFi-GAN vocoder decoder (models/vocoder/HiFiGAN.py StreamGenerator) ----------------
+def hfg_conv_step(desc, carry, x, wp, bias=None, res=None, out=None, carry_out=None):
+    """One sel_hfg_conv_step launch on the current stream.
+
+    desc: sel.hfgops.HfgDesc.  x: (B*T, C) new rows, or (B*T, C/G) when
+    in_group_stride is 0; carry: (B, P, C) or None when K = 1; wp: the packed
+    weight (N, K, C/G), all in one dtype.  res ((B*T, N), or (B*T, N/G) when
+    res_group_stride is 0) and out share the output dtype (out's when given,
+    else x's).  Returns (out, carry_out); missing ones are allocated (not with
+    desc.accumulate, which adds into the given out).  carry is not written."""
+    L.need_device(x, wp, carry, bias, res, out, carry_out)
+    G = max(desc.groups, 1)
+    P = (desc.K - 1) * desc.dil
+    B = desc.rows // max(desc.T, 1)
+    if out is None:
+        if desc.accumulate:
+            raise L.SelError("sel: hfg_conv_step with accumulate needs the out buffer it adds into")
+        out = torch.empty((desc.rows, desc.N), dtype=x.dtype, device=x.device)
+    if P > 0 and carry_out is None and carry is not None:
+        carry_out = torch.empty_like(carry)
+    cin = desc.C if desc.in_group_stride else desc.C // G
+    nres = desc.N if desc.res_group_stride else desc.N // G
+    for t, n in ((x, desc.rows * cin), (out, desc.rows * desc.N), (res, desc.rows * nres), (carry, B * P * desc.C),
+                 (carry_out, B * P * desc.C), (wp, desc.N * desc.K * (desc.C // G))):
+        if t is not None and (not t.is_contiguous() or t.numel() != n):
+            raise L.SelError(f"sel: hfg_conv_step operand of {t.numel()} elements, expected {n} contiguous")
+    if wp.dtype != x.dtype or (carry is not None and carry.dtype != x.dtype) or \
+            (carry_out is not None and carry_out.dtype != x.dtype) or (res is not None and res.dtype != out.dtype):
+        raise L.SelError("sel: hfg_conv_step operands must share the input dtype (res: the output dtype)")
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
+        raise L.SelError("sel: hfg_conv_step takes a contiguous fp32 bias")
+    L.call("sel_hfg_conv_step", ctypes.byref(desc), CO._code(x.dtype), CO._code(out.dtype), L.ptr(carry), L.ptr(x),
+           L.ptr(wp), L.ptr(bias), L.ptr(res), L.ptr(out), L.ptr(carry_out), L.stream())
+    return out, carry_out
+
+
+@dataclass(frozen=True)
+class VocoderStep:
+    """One sel_hfg_conv_step launch of a vocoder hop."""
+    name: str                 # module path of the layer (it owns pad_buffer), generator.get_submodule(name)
+    conv: str                 # module path of the inner nn.Conv1d / nn.ConvTranspose1d: its weight-norm-folded
+    #                           weight comes from sel.hfgops.packed(module, kind, stride, dtype), its bias as is
+    kind: int                 # sel.convops.PACK_FWD / PACK_CONVT
+    stride: int
+    T: int                    # descriptor fields; rows = batch * T
+    C: int
+    N: int
+    K: int
+    dil: int
+    groups: int
+    shared_in: bool           # in_group_stride 0: the source has C/G channels every group reads
+    shared_res: bool          # res_group_stride 0: the residual has N/G channels
+    bias_period: int
+    slope: float              # LeakyReLU slope of the prologue on the new rows (1: none)
+    tanh: bool
+    scale: float
+    accumulate: bool
+    src: int                  # index of the step whose output buffer is the input; -1: decode's input
+    res: Optional[int]        # index of the step whose output buffer is added
+    out: int                  # index of the step whose output buffer this step writes (its own unless accumulate)
+    carry_shape: Optional[Tuple[int, int, int]]   # (batch, P, C) or None (K = 1)
+    buffer: Optional[str]     # state_dict key of the pad_buffer the carry stands for
+    buffer_shape: Optional[Tuple[int, int, int]]  # its shape in the reference: (1, C, P)
+    out_float: bool           # fp32 output whatever the compute dtype
+
+    @property
+    def pad(self):
+        return (self.K - 1) * self.dil
+
+    def desc(self, batch):
+        from . import hfgops as HF
+        return HF.make_desc(batch * self.T, self.T, self.C, self.N, self.K, self.dil, self.pad, CO.PAD_ZERO,
+                            self.groups, self.shared_in, self.shared_res, self.bias_period, 0, self.tanh,
+                            self.accumulate, self.slope, self.scale)
+
+
+@dataclass(frozen=True)
+class VocoderPlan:
+    batch: int
+    frames: int               # input frames per hop
+    in_channels: int
+    out_channels: int
+    out_samples: int          # samples decode() returns per hop: frames * prod(upsample_scales)
+    steps: Tuple[VocoderStep, ...]
+
+
+def _vreject(msg):
+    raise NotImplementedError(f"sel.streamops.plan_vocoder: {msg}")
+
+
+def _lrelu_slope(act, where):
+    if not isinstance(act, torch.nn.LeakyReLU):
+        _vreject(f"{where} is a {type(act).__name__}: the step kernel fuses LeakyReLU only")
+    return float(act.negative_slope)
+
+
+class _VocoderBuilder:
+    def __init__(self, batch):
+        self.batch = batch
+        self.steps = []
+
+    def _add(self, **kw):
+        i = len(self.steps)
+        kw.setdefault("out", i)
+        self.steps.append(VocoderStep(**kw))
+        return kw["out"]
+
+    def causal(self, name, m, T, src, slope=1.0, res=None, shared_in=False, shared_res=False, tanh=False, scale=1.0,
+               out=None, out_float=False):
+        """CausalConv1d.inference fed with act(x) (hfgops.causal_stream)."""
+        from layers.conv_layer import CausalConv1d
+        if not isinstance(m, CausalConv1d) or m.stride != 1:
+            _vreject(f"{name} is no stride-1 CausalConv1d")
+        c = m.conv
+        K, dil = c.kernel_size[0], c.dilation[0]
+        P = (K - 1) * dil
+        if P == 0:
+            _vreject(f"{name} has kernel_size 1: its pad_buffer grows with every call in the reference")
+        kw = {} if out is None else dict(out=out)
+        return self._add(name=name, conv=f"{name}.conv", kind=CO.PACK_FWD, stride=1, T=T, C=c.in_channels,
+                         N=c.out_channels, K=K, dil=dil, groups=c.groups, shared_in=shared_in, shared_res=shared_res,
+                         bias_period=c.out_channels if c.bias is not None else 0, slope=slope, tanh=tanh,
+                         scale=scale, accumulate=out is not None, src=src, res=res,
+                         carry_shape=(self.batch, P, c.in_channels), buffer=f"{name}.pad_buffer",
+                         buffer_shape=(1, c.in_channels, P), out_float=out_float, **kw)
+
+    def upsample(self, name, m, T, src, slope):
+        """CausalConvTranspose1d.inference fed with act(x), k = 2s (hfgops.upsample_stream)."""
+        from layers.conv_layer import CausalConvTranspose1d
+        if not isinstance(m, CausalConvTranspose1d):
+            _vreject(f"{name} is a {type(m).__name__}, not a CausalConvTranspose1d")
+        d, s = m.deconv, m.stride
+        if m.kernel_size != 2 * s or d.groups != 1:
+            _vreject(f"{name} has kernel_size {m.kernel_size} != 2 * stride ({s}) or groups; such layers stay on "
+                     "the module path")
+        i = self._add(name=name, conv=f"{name}.deconv", kind=CO.PACK_CONVT, stride=s, T=T, C=d.in_channels,
+                      N=s * d.out_channels, K=2, dil=1, groups=1, shared_in=False, shared_res=False,
+                      bias_period=d.out_channels if d.bias is not None else 0, slope=slope, tanh=False, scale=1.0,
+                      accumulate=False, src=src, res=None, carry_shape=(self.batch, 1, d.in_channels),
+                      buffer=f"{name}.pad_buffer", buffer_shape=(1, d.in_channels, 1), out_float=False)
+        return i, T * s
+
+    def pointwise(self, name, c, T, src):
+        """Conv1d1x1 (MultiGroupConv1d.conv_out): K = 1, no carry."""
+        if not isinstance(c, torch.nn.Conv1d) or c.kernel_size[0] != 1 or c.groups != 1:
+            _vreject(f"{name} is no 1x1 conv")
+        return self._add(name=name, conv=name, kind=CO.PACK_FWD, stride=1, T=T, C=c.in_channels, N=c.out_channels,
+                         K=1, dil=1, groups=1, shared_in=False, shared_res=False,
+                         bias_period=c.out_channels if c.bias is not None else 0, slope=1.0, tanh=False, scale=1.0,
+                         accumulate=False, src=src, res=None, carry_shape=None, buffer=None, buffer_shape=None,
+                         out_float=False)
+
+    def resblock(self, name, blk, T, src, shared_first=False, scale=1.0, out=None):
+        """HiFiGANResidualBlock.inference (hfgops.resblock, stream=True); shared_first:
+        src has C/G channels (MultiGroupConv1d's repeat, never materialised)."""
+        slope = _lrelu_slope(blk.activation, f"{name}.activation")
+        n = blk.num_layer
+        x = src
+        for idx in range(n):
+            sh = shared_first and idx == 0
+            kw = dict(scale=scale, out=out) if idx == n - 1 else {}
+            if blk.use_additional_convs:
+                h = self.causal(f"{name}.convs1.{idx}", blk.convs1[idx], T, x, slope, shared_in=sh)
+                x = self.causal(f"{name}.convs2.{idx}", blk.convs2[idx], T, h, slope, res=x, shared_res=sh, **kw)
+            else:
+                x = self.causal(f"{name}.convs1.{idx}", blk.convs1[idx], T, x, slope, res=x, shared_in=sh,
+                                shared_res=sh, **kw)
+        return x
+
+
+def plan_vocoder(generator, batch, frames):
+    """The steps of one hop of `frames` input frames at `batch` streams for a
+    HiFi-GAN StreamGenerator (models/vocoder/HiFiGAN.py), in the order of
+    ``decode``: input_conv, per stage the upsampling layer and its block
+    (MultiGroupConv1d: the residual block with the shared input / residual on its
+    first layer, then conv_out; MultiReceptiveField: every block in turn, the
+    first one's last conv writing the fusion buffer at 1/num_blocks, the later
+    ones accumulating into it), output_conv with tanh and fp32 output.  Pure
+    Python: reads module attributes only.  Raises NotImplementedError for what
+    a session cannot run."""
+    from models.vocoder.modules.multi_fusion import MultiGroupConv1d, MultiReceptiveField
+    if batch < 1 or frames < 1:
+        raise ValueError("sel.streamops.plan_vocoder: batch and frames must be positive")
+    for attr in ("input_conv", "upsamples", "blocks", "output_conv", "activation_upsamples", "activation_output1"):
+        if not hasattr(generator, attr):
+            _vreject(f"{type(generator).__name__} is no HiFi-GAN generator (no {attr})")
+    b = _VocoderBuilder(batch)
+    T = frames
+    cur = b.causal("input_conv", generator.input_conv, T, -1)
+    up = _lrelu_slope(generator.activation_upsamples, "activation_upsamples")
+    for i, (ups, blk) in enumerate(zip(generator.upsamples, generator.blocks)):
+        cur, T = b.upsample(f"upsamples.{i}", ups, T, cur, up)
+        if isinstance(blk, MultiGroupConv1d):
+            y = b.resblock(f"blocks.{i}", blk, T, cur, shared_first=True)
+            cur = b.pointwise(f"blocks.{i}.conv_out", blk.conv_out, T, y)
+        elif isinstance(blk, MultiReceptiveField):
+            nb = len(blk.blocks)
+            fused = None
+            for j, rb in enumerate(blk.blocks):
+                o = b.resblock(f"blocks.{i}.blocks.{j}", rb, T, cur, scale=1.0 / nb, out=fused)
+                fused = o if fused is None else fused
+            cur = fused
+        else:
+            _vreject(f"blocks.{i} is a {type(blk).__name__}")
+    out_slope = _lrelu_slope(generator.activation_output1, "activation_output1")
+    if not isinstance(generator.activation_output2, torch.nn.Tanh):
+        _vreject("activation_output2 is not Tanh")
+    b.causal("output_conv", generator.output_conv, T, cur, out_slope, tanh=True, out_float=True)
+    steps = tuple(b.steps)
+    return VocoderPlan(batch, frames, steps[0].C, steps[-1].N, T, steps)

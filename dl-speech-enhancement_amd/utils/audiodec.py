@@ -5,7 +5,8 @@ layout (``torch.load(path)['model']['generator']``, ``config.yml`` beside it).
 Decoder types ``symAudioDec*`` are this project's AudioDec ``StreamGenerator``;
 ``HiFiGAN`` / ``UnivNet`` are ``models.vocoder.HiFiGAN.StreamGenerator`` on its
 own inference path.  One addition: ``open_session`` returns the transmitter's
-and the receiver's ``sel.streaming.StreamSession`` after the reference's warm-up.
+``sel.streaming.StreamSession`` and the receiver's session (a ``StreamSession``,
+or a ``VocoderSession`` for a vocoder decoder) after the reference's warm-up.
 ``AudioDecStreamer`` (the sound-device loop) is not provided.
 """
 import os
@@ -49,18 +50,24 @@ class AudioDec(AudioCodec):
         """(tx, rx) streaming sessions, warmed up as load_transmitter / load_receiver
         left the models: ``tx.encode -> tx.quantize`` on the transmitter,
         ``rx.lookup -> rx.decode`` on the receiver.  The receiver's session runs
-        the lookup on rx_encoder's codebook and the decode on the decoder, which
-        must be an AudioDec generator (the HiFi-GAN vocoder decoder stays on its
-        module path: ``rx_encoder.lookup`` / ``decoder.decode``)."""
-        from sel.streaming import StreamSession
+        the lookup on rx_encoder's codebook and the decode on the decoder: a
+        ``StreamSession`` for an AudioDec generator, a ``VocoderSession`` of
+        ``chunk / hop`` frames per hop for the HiFi-GAN vocoder decoder (hop =
+        the product of its upsample scales)."""
+        from sel.streaming import StreamSession, VocoderSession
         if self.tx_encoder is None or self.rx_encoder is None or self.decoder is None:
             raise RuntimeError("open_session: call load_transmitter and load_receiver first")
-        if not isinstance(self.decoder, generator_audiodec):
-            raise NotImplementedError("open_session: the vocoder decoder has no step-kernel session yet; "
-                                      "use rx_encoder.lookup / decoder.decode")
         tx = StreamSession(self.tx_encoder, batch, chunk, graph)
         tx.load_state()
-        rx = StreamSession(self.decoder, batch, chunk, graph)
+        if isinstance(self.decoder, generator_audiodec):
+            rx = StreamSession(self.decoder, batch, chunk, graph)
+        else:
+            hop = 1
+            for up in self.decoder.upsamples:
+                hop *= up.stride
+            if chunk % hop:
+                raise ValueError(f"open_session: chunk ({chunk}) is not a multiple of the vocoder's hop ({hop})")
+            rx = VocoderSession(self.decoder, batch, chunk // hop, graph)
         rx.load_state()
         rx.lookup_generator = self.rx_encoder
         return tx, rx

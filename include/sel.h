@@ -698,6 +698,49 @@ int sel_hfg_conv_fwd(const sel_hfg_conv_desc* d, int in_dtype, int out_dtype, co
 int sel_hfg_reslayer_fwd(const sel_hfg_conv_desc* d1, int dtype, const void* x, const void* w1pack, const float* b1,
                          const void* w2pack, const float* b2, void* out, sel_stream_t stream);
 
+/* ---- HiFi-GAN vocoder generator, streaming step (HiFiGAN.py:266-305
+ * StreamGenerator.decode, residual_block.py:100-106, multi_fusion.py:119-141) --
+ * One causal layer of one vocoder hop on channels-last rows: the grouped
+ * primitive of sel_hfg_conv_fwd with the reference's pad_buffer as an explicit
+ * carry, as sel_conv_step is to sel_conv_fwd.  Same descriptor:
+ *   T = d->T NEW rows per sample, B = d->rows / T, P = (K-1)*dil;
+ *   required (SEL_ERR_ARG otherwise): T_out 0 or T, pad == P, pad_mode
+ *   SEL_PAD_ZERO, act_skip == 0 (the carry is the skipped part);
+ *   v[b] = [ carry[b] (P rows of pitch C) | act(in[b]) (T rows) ],
+ *          act(x) = x >= 0 ? x : act_slope * x on the NEW rows only: the carry
+ *          holds what pad_buffer holds, the ACTIVATED tail (act_slope 1 = identity);
+ *   out[m, n] = epi( sum_{k<K} sum_{c<C/G} Wp[n][k][c] * v[b, t + k*dil, g*(C/G) + c] ),
+ *          g = n / (N/G), m = b*T + t, epi as sel_hfg_conv_fwd and in its order:
+ *          + bias[n % bias_period], + res[m, g*res_group_stride + n % (N/G)],
+ *          tanh when tanh_out, * out_scale, + out[m, n] when accumulate;
+ *   in_group_stride 0: the new rows have pitch C/G and every group reads them
+ *          (MultiGroupConv1d's x.repeat(1, groups, 1) without the copy).  The
+ *          carry ALWAYS has pitch C (it stands for a state_dict entry), so
+ *          carry_out then holds the activated new rows once per group.
+ *          res_group_stride 0 likewise: res of pitch N/G;
+ *   carry_out[b] = the last P rows of v[b], in in_dtype, written with the act()
+ *          the operand uses: bit for bit what the conv consumed (T < P keeps
+ *          P - T rows of the old carry).  carry is never written; carry_out must
+ *          not alias carry, in or res, out must not alias any input (SEL_ERR_ARG).
+ *          K = 1: P = 0, carry and carry_out may be NULL.
+ * Wp is what sel_pack_weight writes: SEL_PACK_FWD with cin = C/G for the causal
+ * convs; SEL_PACK_CONVT for the upsampling layers, a 2-tap conv with N = s*Cout,
+ * P = 1 and bias_period = Cout, out viewed as (T*s, Cout).
+ * CONTRACT (bf16), as sel_hfg_conv_fwd: act(v) is rounded to bf16 once, products
+ * accumulate in fp32; res, the accumulated out and the result are rounded to
+ * the output type once each.  in_dtype / out_dtype: fp32 -> fp32, bf16 -> bf16
+ * or fp32; res and an accumulated out have the output type.
+ * Any C/G and N/G: ceil((N/G)/16) masked column tiles per group; (C/G) % 8 == 0
+ * with 16-byte aligned pointers takes 16-byte operand loads.  The K*(C/G)
+ * reduction is split over the waves of a block by K*(C/G) alone and summed in
+ * wave order: no atomics, no workspace, two calls give the same bits, and an
+ * output does not depend on B, T or the group count.  Arguments (C % G, N % G,
+ * the group strides, the dtypes, the aliasing rules) are validated before any
+ * device work. */
+int sel_hfg_conv_step(const sel_hfg_conv_desc* d, int in_dtype, int out_dtype, const void* carry, const void* in,
+                      const void* wpack, const float* bias, const void* res, void* out, void* carry_out,
+                      sel_stream_t stream);
+
 /* ---- HiFi-GAN vocoder generator, backward of the grouped primitive ---------
  * Same descriptor, same channels-last lowering.  Write the forward as
  *   out = prev*[accumulate] + out_scale * tanh?( conv(act(x)) + bias + res );
