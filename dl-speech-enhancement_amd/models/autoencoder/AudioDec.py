@@ -105,6 +105,13 @@ class StreamGenerator(Generator):
         from sel.streaming import StreamSession
         return StreamSession(self, batch, chunk, graph)
 
+    def pool(self, capacity, chunk=300, graph=True, dtype=None):
+        """An opt-in sel.streaming.StreamPool over this generator: `capacity`
+        independent streams that open, close and tick on their own, one batched
+        hop per tick over the active ones."""
+        from sel.streaming import StreamPool
+        return StreamPool(self, capacity, chunk, graph, dtype)
+
     def reset_buffer(self):
         """Zero every causal layer's pad_buffer (AudioDec.py:185-191)."""
         from layers.conv_layer import CausalConv1d, CausalConvTranspose1d

@@ -58,3 +58,4 @@ class StreamGenerator(Generator):
 
     reset_buffer = _PQCStream.reset_buffer
     session = _PQCStream.session
+    pool = _PQCStream.pool

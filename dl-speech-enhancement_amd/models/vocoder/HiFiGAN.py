@@ -231,6 +231,12 @@ class StreamGenerator(Generator):
         from sel.streaming import VocoderSession
         return VocoderSession(self, batch, frames, graph)
 
+    def pool(self, capacity, frames=1, graph=True, dtype=None):
+        """An opt-in sel.streaming.VocoderPool over this generator: `capacity`
+        independent streams, one batched hop per tick over the active ones."""
+        from sel.streaming import VocoderPool
+        return VocoderPool(self, capacity, frames, graph, dtype)
+
     def reset_buffer(self):
         """Zero every streaming pad_buffer."""
 

@@ -126,6 +126,9 @@ SIGNATURES = {
     "sel_conv_step": (I32, [P, I32, I32, P, P, P, P, P, P, P, P]),
     "sel_stream_commit": (I32, [P, I32, P]),
     "sel_hfg_conv_step": (I32, [P, I32, I32, P, P, P, P, P, P, P, P]),
+    "sel_conv_step_pool": (I32, [P, I32, I32, P, P, I32, P, P, P, P, P, P, P, P]),
+    "sel_stream_copy_slots": (I32, [P, I32, I32, P, P, I32, P, P]),
+    "sel_hfg_conv_step_pool": (I32, [P, I32, I32, P, P, I32, P, P, P, P, P, P, P, P]),
 }
 
 _lock = threading.Lock()

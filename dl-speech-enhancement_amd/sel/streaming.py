@@ -18,6 +18,12 @@ HiFi-GAN vocoder ``StreamGenerator.decode`` (models/vocoder/HiFiGAN.py): one
 ``sel_hfg_conv_step`` launch per conv (csrc/hfg_step.hip; groups, LeakyReLU,
 tanh and the MultiReceptiveField mean inside the kernel), one commit per 48
 carries, one graph.
+
+``StreamPool`` / ``VocoderPool`` serve streams that do NOT move in lockstep:
+a fixed number of slots, each holding one stream's carries, and per tick one
+batched hop over whichever slots have a hop ready, on the slot-indexed step
+kernels (``sel_conv_step_pool`` / ``sel_hfg_conv_step_pool``); the active set is
+device data, so one captured graph serves every tick.
 """
 import torch
 
@@ -345,3 +351,291 @@ class VocoderSession:
         """The generator's pad_buffers <- carries, in the reference's shapes (fp32)."""
         for _, c, m in self._layers():
             m.pad_buffer = c.transpose(1, 2).float().contiguous()
+
+
+# ---- stream pools: independent streams on the slot-indexed step kernels -------------------------
+class _Stager:
+    """The per-tick control words of a pool: ``[n, slot_0, slot_1, ...]`` goes
+    from pinned host memory into a fixed device buffer with one asynchronous
+    copy on the current stream, outside the graph.  The pinned side is a small
+    ring; an entry is reused only after the event recorded behind its last copy
+    has completed, so a pending copy never sees its source overwritten."""
+    RING = 4
+
+    def __init__(self, width, device):
+        self.width = width
+        self.host = [torch.zeros(width, dtype=torch.int32).pin_memory() for _ in range(self.RING)]
+        self.events = [None] * self.RING
+        self.turn = 0
+        self.device = device
+
+    def stage(self, dst, words):
+        if len(words) > self.width or dst.numel() > self.width:
+            raise L.SelError(f"sel: {len(words)} control words for a staging ring of {self.width}")
+        k = self.turn
+        self.turn = (k + 1) % self.RING
+        if self.events[k] is not None:
+            self.events[k].synchronize()
+        h = self.host[k]
+        h.zero_()
+        h[:len(words)] = torch.tensor(words, dtype=torch.int32)
+        dst.copy_(h[:dst.numel()], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self.events[k] = ev
+
+
+class _PoolMixin:
+    """What _PoolHalf and _VocoderPoolHalf add to their session halves: carry
+    pools of capacity + 1 slot rows, the device control words and the
+    slot-indexed launches."""
+
+    def _make_pool(self, capacity, device):
+        self.capacity = capacity
+        self.nslots = capacity + 1          # row `capacity` is the template
+        self.ctl = torch.zeros(1 + capacity, dtype=torch.int32, device=device)
+        self.n_active, self.slots = self.ctl[:1], self.ctl[1:]
+        for lst in (self.carry, self.carry_out):
+            for i, c in enumerate(lst):
+                if c is not None:
+                    lst[i] = torch.zeros((self.nslots,) + tuple(c.shape[1:]), dtype=c.dtype, device=device)
+        self.pairs = [(o, c) for o, c in zip(self.carry_out, self.carry) if c is not None]
+
+    def launch(self):
+        step = self._step
+        for i, st in enumerate(self.steps):
+            step(self.descs[i], self.carry[i], self.carry_out[i], self.slots, self.n_active, self._buf(st.src),
+                 self.wps[i], self.biases[i], None if st.res is None else self._buf(st.res), self.outs[i],
+                 nslots=self.nslots)
+        SO.copy_slots(self.pairs, self.slots, self.slots, self.n_active)
+
+class _PoolHalf(_PoolMixin, _Half):
+    _step = staticmethod(SO.conv_step_pool)
+
+    def __init__(self, steps, generator, capacity, in_channels, dtype, device):
+        _Half.__init__(self, steps, generator, capacity, in_channels, dtype, device)
+        self._make_pool(capacity, device)
+
+
+class _VocoderPoolHalf(_PoolMixin, _VocoderHalf):
+    _step = staticmethod(SO.hfg_conv_step_pool)
+
+    def __init__(self, steps, generator, capacity, in_channels, dtype, device):
+        _VocoderHalf.__init__(self, steps, generator, capacity, in_channels, dtype, device)
+        self._make_pool(capacity, device)
+
+
+class _PoolBase:
+    """Slots, the template row, staging and opening: shared by StreamPool and VocoderPool."""
+
+    def _init_pool(self, capacity, halves, device):
+        self.capacity = int(capacity)
+        self.table = SO.SlotTable(capacity)
+        self._halves = halves
+        # the ring carries a tick's [n, slots...] (1 + capacity words) and open()'s
+        # three words below, whichever is longer (capacity 1: three)
+        self._stager = _Stager(max(3, 1 + self.capacity), device)
+        # opening a stream: [1, capacity (the template row), the new slot]
+        self._open_ctl = torch.zeros(3, dtype=torch.int32, device=device)
+        self._carries = [c for h in halves for c in h.carry if c is not None]
+
+    def _capture(self, graph):
+        self.graphed = bool(graph)
+        if graph:
+            # n_active = 0: every block of every launch returns at once, so the
+            # warm-up hops and the capture itself leave no state behind
+            for h in self._halves:
+                h.ctl.zero_()
+                h.capture()
+
+    def _stage(self, half, slots):
+        slots = self.table.check(slots)
+        self._stager.stage(half.ctl, [len(slots)] + slots)
+        return len(slots)
+
+    def _layers(self):
+        for half in self._halves:
+            for st, c in zip(half.steps, half.carry):
+                if c is not None:
+                    yield st, c, self.generator.get_submodule(st.name)
+
+    @torch.no_grad()
+    def open(self):
+        """A free slot (the lowest), its state copied from the template row in one launch."""
+        slot = self.table.open()
+        try:
+            self._stager.stage(self._open_ctl, [1, self.capacity, slot])
+            c = self._open_ctl
+            SO.copy_slots([(t, t) for t in self._carries], c[1:2], c[2:3], c[0:1])
+        except BaseException:
+            self.table.close(slot)      # the slot is taken only once its state is in place
+            raise
+        return slot
+
+    def close(self, slot):
+        self.table.close(slot)
+
+    def state(self, slot):
+        """{pad_buffer key: (P, C) carry of the slot, channels-last} -- a view, for inspection."""
+        slot, = self.table.check([slot])
+        return {st.buffer: c[slot] for st, c, _ in self._layers()}
+
+    @torch.no_grad()
+    def reset_template(self):
+        """New streams start from zero state."""
+        for c in self._carries:
+            c[self.capacity].zero_()
+
+    def _template_rows(self, st, c, m):
+        pb = m.pad_buffer
+        if pb.shape[0] != 1 or tuple(pb.shape[1:]) != tuple(st.buffer_shape[1:]):
+            raise L.SelError(f"sel: {st.buffer} has shape {tuple(pb.shape)}, the pool's template holds "
+                             f"{st.buffer_shape}")
+        return pb.to(c.device).transpose(1, 2)[0]      # (P_ref, Cin)
+
+
+class StreamPool(_PoolBase):
+    """``capacity`` independent streams of one AudioDec ``StreamGenerator``,
+    ``chunk`` samples per hop: streams open and close at any time, and on every
+    tick one batched hop runs over whichever slots have a hop ready.  Every
+    stream's output equals, bit for bit, what a solo ``batch=1`` session gives
+    on the same hops.
+
+    ``slot = open()`` / ``close(slot)``; per tick, for a list ``slots`` of n
+    distinct open slots: ``encode(slots, x)`` with x (n, in_channels, chunk) ->
+    z (n, code_dim, frames); ``quantize(z)`` -> idx (codebooks, n, frames);
+    ``lookup(idx)`` -> (n, frames, dim); ``decode(slots, zq)`` -> y (n,
+    out_channels, samples).  Sample i of every tensor belongs to ``slots[i]``.
+    The tensors ``encode`` and ``decode`` return are VIEWS of the first n samples
+    of the pool's fixed buffers, valid until the next call of the same method.
+
+    The plan is that of a session of ``batch = capacity``.  Every carry and its
+    ``carry_out`` twin holds capacity + 1 slot rows; row ``capacity`` is the
+    TEMPLATE a newly opened stream starts from: zero after construction and
+    ``reset_template()``, the generator's pad_buffers (the reference's warm-up)
+    after ``load_state()``.  ``state(slot)`` shows a stream's carries.
+
+    ``graph=True``: each half is one graph captured once at capacity (with no
+    active stream, so the capture leaves no state behind).  Per tick the list
+    and its length go through pinned host memory (a ring of four entries, each
+    guarded by an event) into fixed device words with one asynchronous copy on
+    the current stream, before the replay and outside the graph; the kernels
+    read them, so one graph serves every active set.  ``graph=False`` issues the
+    same launches eagerly; both produce the same bits."""
+
+    def __init__(self, generator, capacity, chunk=300, graph=True, dtype=None):
+        self.generator = generator
+        self.lookup_generator = generator
+        self.plan = SO.plan(generator, capacity, chunk)
+        self.dtype = dtype or CO.compute_dtype()
+        p = next(generator.parameters())
+        L.need_device(p)
+        L.lib()
+        pl = self.plan
+        with torch.no_grad():
+            self._enc = _PoolHalf(pl.encode, generator, capacity, pl.in_channels, self.dtype, p.device)
+            self._dec = _PoolHalf(pl.decode, generator, capacity, pl.dec_in_channels, self.dtype, p.device)
+            if hasattr(generator, "quantizer") and not hasattr(generator.quantizer.codebook, "codebook_size"):
+                generator.quantizer.initial()
+            self._init_pool(capacity, (self._enc, self._dec), p.device)
+            self._capture(graph)
+
+    @torch.no_grad()
+    def encode(self, slots, x):
+        pl = self.plan
+        L.need_device(x)
+        if tuple(x.shape) != (len(slots), pl.in_channels, pl.chunk):
+            raise L.SelError(f"sel: pool encode takes {(len(slots), pl.in_channels, pl.chunk)} for {len(slots)} "
+                             f"slots, got {tuple(x.shape)}")
+        n = self._stage(self._enc, slots)
+        self._enc.inp[:n].copy_(x.transpose(1, 2))
+        out = self._enc.run()
+        return out.view(self.capacity, pl.frames, pl.enc_channels)[:n].transpose(1, 2)
+
+    @torch.no_grad()
+    def quantize(self, z):
+        """z (n, code_dim, frames) -> flattened code indices (codebooks, n, frames)."""
+        idx = self.lookup_generator.quantize(z)
+        return idx.view(idx.shape[0], z.shape[0], z.shape[2])
+
+    @torch.no_grad()
+    def lookup(self, idx):
+        zq = self.lookup_generator.lookup(idx)
+        return zq.reshape(-1, self.plan.frames, zq.shape[-1])
+
+    @torch.no_grad()
+    def decode(self, slots, zq):
+        pl = self.plan
+        L.need_device(zq)
+        src = zq if pl.pqc else zq.transpose(1, 2)
+        if tuple(src.shape) != (len(slots), pl.frames, pl.dec_in_channels):
+            raise L.SelError(f"sel: pool decode takes {pl.frames} frames of {pl.dec_in_channels} channels for "
+                             f"{len(slots)} slots, got {tuple(zq.shape)}")
+        n = self._stage(self._dec, slots)
+        self._dec.inp[:n].copy_(src)
+        out = self._dec.run()
+        return out.view(self.capacity, pl.out_samples, pl.out_channels)[:n].transpose(1, 2)
+
+    @torch.no_grad()
+    def load_state(self):
+        """template <- the generator's pad_buffers ((1, C, P)), as StreamSession.load_state fills a carry."""
+        for st, c, m in self._layers():
+            rows = self._template_rows(st, c, m)
+            t = c[self.capacity]
+            if st.kind == CO.PACK_FWD_STRIDED:
+                # 2s samples as 2 phase rows; the extra oldest sample meets a zero weight
+                v = t.view(2 * st.stride, -1)
+                v[:1].zero_()
+                v[1:].copy_(rows)
+            else:
+                t.copy_(rows)
+
+
+class VocoderPool(_PoolBase):
+    """``capacity`` independent streams of one HiFi-GAN vocoder ``StreamGenerator``,
+    ``frames`` code frames per hop: StreamPool's slots, template row, staging and
+    graph for ``decode(slots, c)`` with c (n, frames, in_channels) -> y (n,
+    out_channels, samples) fp32, a VIEW of the first n samples of the fixed output
+    buffer.  ``decode_norm`` (the generator's ``stats``) is applied while the
+    input buffer is filled; ``lookup(idx)`` goes through ``lookup_generator`` and
+    returns (n, frames, code_dim)."""
+
+    def __init__(self, generator, capacity, frames=1, graph=True, dtype=None):
+        self.generator = generator
+        self.lookup_generator = None
+        self.plan = SO.plan_vocoder(generator, capacity, frames)
+        self.dtype = dtype or CO.compute_dtype()
+        p = next(generator.parameters())
+        L.need_device(p)
+        L.lib()
+        pl = self.plan
+        with torch.no_grad():
+            self._dec = _VocoderPoolHalf(pl.steps, generator, capacity, pl.in_channels, self.dtype, p.device)
+            self._init_pool(capacity, (self._dec,), p.device)
+            self._capture(graph)
+
+    @torch.no_grad()
+    def lookup(self, idx):
+        if self.lookup_generator is None:
+            raise L.SelError("sel: this VocoderPool has no lookup_generator (the generator whose codebooks "
+                             "decode the indices)")
+        zq = self.lookup_generator.lookup(idx)
+        return zq.reshape(-1, self.plan.frames, zq.shape[-1])
+
+    @torch.no_grad()
+    def decode(self, slots, c):
+        pl = self.plan
+        L.need_device(c)
+        if tuple(c.shape) != (len(slots), pl.frames, pl.in_channels):
+            raise L.SelError(f"sel: pool decode takes {(len(slots), pl.frames, pl.in_channels)} for {len(slots)} "
+                             f"slots, got {tuple(c.shape)}")
+        n = self._stage(self._dec, slots)
+        self._dec.inp[:n].copy_(self.generator.decode_norm(c))
+        out = self._dec.run()
+        return out.view(self.capacity, pl.out_samples, pl.out_channels)[:n].transpose(1, 2)
+
+    @torch.no_grad()
+    def load_state(self):
+        """template <- the generator's pad_buffers ((1, C, P))."""
+        for st, c, m in self._layers():
+            c[self.capacity].copy_(self._template_rows(st, c, m))

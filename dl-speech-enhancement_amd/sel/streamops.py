@@ -14,6 +14,10 @@ executes one on the CPU against the oracle.
 LeakyReLU form of the same step, and ``plan_vocoder`` walks a HiFi-GAN vocoder
 ``StreamGenerator`` (models/vocoder/HiFiGAN.py) the same way;
 tests/test_vocoder_plan_host.py executes its plans against the reference goldens.
+
+``conv_step_pool`` / ``hfg_conv_step_pool`` / ``copy_slots`` bind the
+slot-indexed forms for stream pools (``sel.streaming.StreamPool``), and
+``SlotTable`` is the host-side record of which slots are open.
 """
 import ctypes
 from dataclasses import dataclass
@@ -61,6 +65,157 @@ def commit(pairs):
     jobs = (CopyJob * len(pairs))(*[CopyJob(s.data_ptr(), d.data_ptr(), s.numel() * s.element_size())
                                     for s, d in pairs])
     L.call("sel_stream_commit", ctypes.cast(jobs, ctypes.c_void_p), len(pairs), L.stream())
+
+
+# ---- stream pools: the slot-indexed forms (include/sel.h sel_conv_step_pool) ------------------
+class SlotTable:
+    """Which slots of a pool of ``capacity`` are open.  Pure Python, no device:
+    the kernels trust the list they are given (distinct, in range), so every
+    list passes ``check`` before it is staged."""
+
+    def __init__(self, capacity):
+        if capacity < 1:
+            raise ValueError("sel.streamops.SlotTable: capacity must be positive")
+        self.capacity = int(capacity)
+        self._open = set()
+
+    def open(self):
+        """The lowest free slot."""
+        for s in range(self.capacity):
+            if s not in self._open:
+                self._open.add(s)
+                return s
+        raise L.SelError(f"sel: the pool is full ({self.capacity} streams open)")
+
+    def close(self, slot):
+        self.check([slot])
+        self._open.discard(int(slot))
+
+    def is_open(self, slot):
+        return slot in self._open
+
+    def __len__(self):
+        return len(self._open)
+
+    def check(self, slots):
+        """The list as ints; SelError for a list longer than capacity, a
+        duplicate, an id out of range or a closed slot."""
+        raw = list(slots)      # once: a one-shot iterator must not slip past the checks below
+        out = [int(s) for s in raw]
+        if len(out) > self.capacity:
+            raise L.SelError(f"sel: {len(out)} slots listed, the pool holds {self.capacity}")
+        if len(set(out)) != len(out):
+            raise L.SelError(f"sel: duplicate slot in {out}")
+        for s, r in zip(out, raw):
+            if s != r or not 0 <= s < self.capacity:
+                raise L.SelError(f"sel: slot {r!r} is out of range [0, {self.capacity})")
+            if s not in self._open:
+                raise L.SelError(f"sel: slot {s} is not open")
+        return out
+
+
+def _pool_operands(what, desc, cin, nres, P, carry, carry_out, slots, n_active, x, wp, res, out, nslots):
+    B = desc.rows // max(desc.T, 1)
+    for t in (slots, n_active):
+        if t is None or t.dtype != torch.int32 or not t.is_contiguous():
+            raise L.SelError(f"sel: {what} takes contiguous int32 device tensors for slots and n_active")
+    if slots.numel() < B or n_active.numel() < 1:
+        raise L.SelError(f"sel: {what} needs {B} slot entries (capacity) and one n_active, got "
+                         f"{slots.numel()} and {n_active.numel()}")
+    if P == 0:
+        if nslots is None or nslots < 1:
+            raise L.SelError(f"sel: {what} with K = 1 has no carry pool to size the slot range: pass nslots")
+    else:
+        if carry is None or carry_out is None or carry.shape != carry_out.shape or carry.dim() != 3:
+            raise L.SelError(f"sel: {what} with K > 1 needs carry and carry_out pools of one shape (nslots, P, C)")
+        if nslots not in (None, carry.shape[0]):
+            raise L.SelError(f"sel: {what} nslots {nslots} is not the carry pool's {carry.shape[0]}")
+        nslots = carry.shape[0]
+        if tuple(carry.shape[1:]) != (P, desc.C):
+            raise L.SelError(f"sel: {what} carry pool of shape {tuple(carry.shape)}, expected (nslots, {P}, {desc.C})")
+    for t, n in ((x, desc.rows * cin), (out, desc.rows * desc.N), (res, desc.rows * nres)):
+        if t is not None and (not t.is_contiguous() or t.numel() != n):
+            raise L.SelError(f"sel: {what} operand of {t.numel()} elements, expected {n} contiguous")
+    for t in (carry, carry_out):
+        if t is not None and not t.is_contiguous():
+            raise L.SelError(f"sel: {what} takes contiguous carry pools")
+    if wp.dtype != x.dtype or (carry is not None and carry.dtype != x.dtype) or \
+            (carry_out is not None and carry_out.dtype != x.dtype) or (res is not None and res.dtype != out.dtype):
+        raise L.SelError(f"sel: {what} operands must share the input dtype (res: the output dtype)")
+    return nslots
+
+
+def conv_step_pool(desc, carry, carry_out, slots, n_active, x, wp, bias=None, res=None, out=None, nslots=None):
+    """One sel_conv_step_pool launch on the current stream.
+
+    desc.rows = capacity * T.  carry / carry_out: (nslots, P, C) pools (None when
+    K = 1); slots (>= capacity int32) and n_active (1 int32): DEVICE tensors the
+    kernel reads, so a captured launch follows what is staged into them; x, res,
+    out: the capacity-sized dense buffers, of which the first n_active samples
+    are read / written.  The list must hold distinct ids (SlotTable.check).
+    nslots: the valid slot range when there is no carry pool to take it from (K = 1).
+    Returns out (allocated when missing)."""
+    L.need_device(x, wp, carry, carry_out, slots, n_active, bias, res, out)
+    P = (desc.K - 1) * desc.dil
+    if out is None:
+        out = torch.empty((desc.rows, desc.N), dtype=x.dtype, device=x.device)
+    nslots = _pool_operands("conv_step_pool", desc, desc.C, desc.N, P, carry, carry_out, slots, n_active, x, wp, res,
+                            out, nslots)
+    if wp.numel() != desc.N * desc.K * desc.C:
+        raise L.SelError(f"sel: conv_step_pool weight of {wp.numel()} elements, expected {desc.N * desc.K * desc.C}")
+    L.call("sel_conv_step_pool", ctypes.byref(desc), CO._code(x.dtype), CO._code(out.dtype), L.ptr(carry),
+           L.ptr(carry_out), nslots, L.ptr(slots), L.ptr(n_active), L.ptr(x), L.ptr(wp), L.ptr(bias), L.ptr(res),
+           L.ptr(out), L.stream())
+    return out
+
+
+def hfg_conv_step_pool(desc, carry, carry_out, slots, n_active, x, wp, bias=None, res=None, out=None,
+                       nslots=None):
+    """One sel_hfg_conv_step_pool launch on the current stream: hfg_conv_step's
+    operands with conv_step_pool's slot table (carry pools (nslots, P, C))."""
+    L.need_device(x, wp, carry, carry_out, slots, n_active, bias, res, out)
+    G = max(desc.groups, 1)
+    P = (desc.K - 1) * desc.dil
+    if out is None:
+        if desc.accumulate:
+            raise L.SelError("sel: hfg_conv_step_pool with accumulate needs the out buffer it adds into")
+        out = torch.empty((desc.rows, desc.N), dtype=x.dtype, device=x.device)
+    cin = desc.C if desc.in_group_stride else desc.C // G
+    nres = desc.N if desc.res_group_stride else desc.N // G
+    nslots = _pool_operands("hfg_conv_step_pool", desc, cin, nres, P, carry, carry_out, slots, n_active, x, wp, res,
+                            out, nslots)
+    if wp.numel() != desc.N * desc.K * (desc.C // G):
+        raise L.SelError(f"sel: hfg_conv_step_pool weight of {wp.numel()} elements, expected "
+                         f"{desc.N * desc.K * (desc.C // G)}")
+    if bias is not None and (bias.dtype != torch.float32 or not bias.is_contiguous()):
+        raise L.SelError("sel: hfg_conv_step_pool takes a contiguous fp32 bias")
+    L.call("sel_hfg_conv_step_pool", ctypes.byref(desc), CO._code(x.dtype), CO._code(out.dtype), L.ptr(carry),
+           L.ptr(carry_out), nslots, L.ptr(slots), L.ptr(n_active), L.ptr(x), L.ptr(wp), L.ptr(bias), L.ptr(res),
+           L.ptr(out), L.stream())
+    return out
+
+
+def copy_slots(pairs, src_slots, dst_slots, n):
+    """Slot row src_slots[i] of src -> slot row dst_slots[i] of dst for every
+    (src, dst) pair of pools (nslots, ...) and i < n[0], one launch per 48 pairs.
+    src_slots / dst_slots / n are int32 DEVICE tensors read by the kernel.  All
+    pools share nslots; src may be dst (opening a stream from the template row)."""
+    L.need_device(src_slots, dst_slots, n, *[t for p in pairs for t in p])
+    for t in (src_slots, dst_slots, n):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise L.SelError("sel: copy_slots takes contiguous int32 device tensors for the slot lists and n")
+    nslots = pairs[0][0].shape[0]
+    for s, d in pairs:
+        if s.shape != d.shape or s.dtype != d.dtype or s.shape[0] != nslots or not s.is_contiguous() \
+                or not d.is_contiguous():
+            raise L.SelError("sel: copy_slots pairs must be contiguous pools of one shape, dtype and slot count")
+    cap = min(src_slots.numel(), dst_slots.numel())
+    if cap < 1 or n.numel() < 1:
+        raise L.SelError("sel: copy_slots needs non-empty slot lists and a count")
+    jobs = (CopyJob * len(pairs))(*[CopyJob(s.data_ptr(), d.data_ptr(), s[0].numel() * s.element_size())
+                                    for s, d in pairs])
+    L.call("sel_stream_copy_slots", ctypes.cast(jobs, ctypes.c_void_p), len(pairs), nslots, L.ptr(src_slots),
+           L.ptr(dst_slots), cap, L.ptr(n), L.stream())
 
 
 @dataclass(frozen=True)

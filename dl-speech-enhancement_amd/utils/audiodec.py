@@ -6,7 +6,8 @@ Decoder types ``symAudioDec*`` are this project's AudioDec ``StreamGenerator``;
 ``HiFiGAN`` / ``UnivNet`` are ``models.vocoder.HiFiGAN.StreamGenerator`` on its
 own inference path.  One addition: ``open_session`` returns the transmitter's
 ``sel.streaming.StreamSession`` and the receiver's session (a ``StreamSession``,
-or a ``VocoderSession`` for a vocoder decoder) after the reference's warm-up.
+or a ``VocoderSession`` for a vocoder decoder) after the reference's warm-up,
+and ``open_pool`` the same pair as stream pools for independent streams.
 ``AudioDecStreamer`` (the sound-device loop) is not provided.
 """
 import os
@@ -68,6 +69,30 @@ class AudioDec(AudioCodec):
             if chunk % hop:
                 raise ValueError(f"open_session: chunk ({chunk}) is not a multiple of the vocoder's hop ({hop})")
             rx = VocoderSession(self.decoder, batch, chunk // hop, graph)
+        rx.load_state()
+        rx.lookup_generator = self.rx_encoder
+        return tx, rx
+
+    def open_pool(self, capacity, chunk=300, graph=True):
+        """(tx_pool, rx_pool) for `capacity` independent streams, mirroring
+        open_session: a ``StreamPool`` on the transmitter, a ``StreamPool`` or a
+        ``VocoderPool`` (``chunk / hop`` frames per hop) on the receiver, both
+        with the models' warmed-up pad_buffers as the template every newly
+        opened stream starts from."""
+        from sel.streaming import StreamPool, VocoderPool
+        if self.tx_encoder is None or self.rx_encoder is None or self.decoder is None:
+            raise RuntimeError("open_pool: call load_transmitter and load_receiver first")
+        tx = StreamPool(self.tx_encoder, capacity, chunk, graph)
+        tx.load_state()
+        if isinstance(self.decoder, generator_audiodec):
+            rx = StreamPool(self.decoder, capacity, chunk, graph)
+        else:
+            hop = 1
+            for up in self.decoder.upsamples:
+                hop *= up.stride
+            if chunk % hop:
+                raise ValueError(f"open_pool: chunk ({chunk}) is not a multiple of the vocoder's hop ({hop})")
+            rx = VocoderPool(self.decoder, capacity, chunk // hop, graph)
         rx.load_state()
         rx.lookup_generator = self.rx_encoder
         return tx, rx

@@ -315,6 +315,45 @@ typedef struct sel_copy_job {
 } sel_copy_job;
 int sel_stream_commit(const sel_copy_job* jobs, int njobs, sel_stream_t stream);
 
+/* ---- stream pools: independent streams on slot-indexed steps ----------------
+ * sel_conv_step with a slot table: one batched step over whichever streams have
+ * a hop ready on this tick.  d->rows = capacity * T sizes the launch (grid, the
+ * RT switch) and never changes; the wave count depends on K*C alone.
+ *   slots     DEVICE int32[>= capacity], n_active DEVICE int32 (both required);
+ *   n = min(*n_active, capacity) samples exist on this tick (negative: 0);
+ *   sample i reads its T new rows at in[i*T ..] (res likewise) and writes
+ *          out[i*T ..]: in / res / out are DENSE in active order;
+ *   sample i reads its P carried rows at carry[slots[i]] and writes
+ *          carry_out[slots[i]]: both are pools of nslots (> 0) slot rows of pitch
+ *          P*C elements, in in_dtype.
+ * Row groups that lie entirely at or beyond n*T return before any load (conv
+ * blocks and carry-writer blocks alike); nothing is written for rows >= n*T of
+ * out nor for a slot that is not in the list.  A list entry outside [0, nslots)
+ * makes that sample absent -- nothing is read through it, nothing is written for
+ * it: a guard, not a feature.  Entries must be distinct (two samples on one
+ * slot race on carry_out; sel.streamops.SlotTable enforces it).
+ * Everything else is sel_conv_step's and validated before any device work: the
+ * dtypes, the aliasing rules, K = 1 with NULL pools, the pack kinds, the 16-byte
+ * fast path (C % 8 == 0, aligned in / wpack / carry).  The output rows and the
+ * carry_out row of sample i are, bit for bit, what sel_conv_step gives at B = 1
+ * on that slot's carry and those input rows. */
+int sel_conv_step_pool(const sel_conv_desc* d, int in_dtype, int out_dtype, const void* carry, void* carry_out,
+                       int nslots, const int32_t* slots, const int32_t* n_active, const void* in, const void* wpack,
+                       const float* bias, const void* res, void* out, sel_stream_t stream);
+/* Slot rows between pools: for i < min(*n, cap) and every job, slot row
+ * src_slots[i] of job.src -> slot row dst_slots[i] of job.dst, where job.bytes
+ * is the pitch of one slot row and both pools hold nslots rows.  `jobs` is a
+ * HOST array (copied into the kernel arguments, 48 per launch); src_slots,
+ * dst_slots (DEVICE int32[>= cap]) and n (DEVICE int32) are read by the kernel,
+ * so one captured launch serves every tick.  16-byte vectors where both rows
+ * are 16-byte aligned, then a byte tail; an entry outside [0, nslots) skips its
+ * row.  Two uses: the commit of a pool hop (carry_out -> carry with src_slots =
+ * dst_slots = the tick's list) and opening a stream (the template row of every
+ * carry -> the new slot; src and dst may then be the same pool -- rows must not
+ * overlap, i.e. no dst_slots entry equals a src_slots entry of another i). */
+int sel_stream_copy_slots(const sel_copy_job* jobs, int njobs, int nslots, const int32_t* src_slots,
+                          const int32_t* dst_slots, int cap, const int32_t* n, sel_stream_t stream);
+
 /* ---- residual VQ: layers/vq_module.py:61-88 (eval), :119-134 -------------
  * All stages of one row block in one launch (rows are independent):
  *   dist_k = (|r|^2 - (2r).e_k) + |e_k|^2, idx = argmin (lowest index on ties),
@@ -740,6 +779,18 @@ int sel_hfg_reslayer_fwd(const sel_hfg_conv_desc* d1, int dtype, const void* x, 
 int sel_hfg_conv_step(const sel_hfg_conv_desc* d, int in_dtype, int out_dtype, const void* carry, const void* in,
                       const void* wpack, const float* bias, const void* res, void* out, void* carry_out,
                       sel_stream_t stream);
+/* sel_hfg_conv_step with a slot table, exactly as sel_conv_step_pool extends
+ * sel_conv_step: d->rows = capacity * T, dense in / res / out in active order
+ * (in_group_stride / res_group_stride 0, accumulate, tanh_out and out_scale as
+ * in the session form; an accumulated out is read and written for the first
+ * n*T rows only), carry / carry_out pools of nslots slot rows of pitch P*C
+ * (the carry pitch is C, as now), n = min(*n_active, capacity), early return of
+ * row groups at or beyond n*T, entries outside [0, nslots) absent.  Bit for
+ * bit sel_hfg_conv_step at B = 1 per sample. */
+int sel_hfg_conv_step_pool(const sel_hfg_conv_desc* d, int in_dtype, int out_dtype, const void* carry,
+                           void* carry_out, int nslots, const int32_t* slots, const int32_t* n_active,
+                           const void* in, const void* wpack, const float* bias, const void* res, void* out,
+                           sel_stream_t stream);
 
 /* ---- HiFi-GAN vocoder generator, backward of the grouped primitive ---------
  * Same descriptor, same channels-last lowering.  Write the forward as

@@ -24,6 +24,26 @@ vocoder decoders instead -- module path (StreamGenerator.decode), eager
 sel.streaming.VocoderSession, graph replay, same protocol -- and writes
 profiles/stream_bench_vocoder.{json,md} (the table of DESIGN §14); its
 acceptance line compares replay with module at B = 1, one frame.
+
+  python tools/stream_bench.py --pool
+measures what N independent streams cost per tick (default N = 16, chunk 300;
+the transmitter half and the v1 vocoder receiver half), four paths alternating
+in one process, same protocol:
+
+  solo      N batch=1 graph sessions stepped one after the other
+  lockstep  one batch=N graph session (streams that cannot start or stop alone)
+  pool      sel.streaming.StreamPool / VocoderPool, N of N slots active
+  pool_k    the same pool with --active (default 4) of N slots active
+
+and writes profiles/stream_pool_bench.{json,md} (the table of DESIGN §15); its
+acceptance line compares pool with solo.
+
+  python tools/stream_bench.py --pool --attribution
+splits the pool's extra time over the lockstep session (all N slots active)
+into its parts, same protocol: the two graphs replayed alone, the same graphs
+captured without their commit / copy_slots launch, and the full calls (input
+fill + replay, and for the pool the staging of the slot list); writes
+profiles/stream_pool_attribution.{json,md} (the second table of DESIGN §15.3).
 """
 import argparse
 import json
@@ -151,6 +171,198 @@ def run_vocoder_config(decoder, dtype, B, chunk, hops, warmup, rate, dev):
                 chunk_ms=dur_ms, paths=out)
 
 
+def run_pool_config(half, dtype, N, active, chunk, hops, warmup, dev):
+    """One tick of N independent streams, `half` = "tx" (AudioDec encode +
+    quantize) or "rx_v1" (lookup + v1 vocoder decode), at full width."""
+    from models.autoencoder.AudioDec import StreamGenerator as Encoder
+    from models.vocoder.HiFiGAN import StreamGenerator as Vocoder
+    from sel import configs
+    from sel.streaming import StreamPool, StreamSession, VocoderPool, VocoderSession
+    torch.manual_seed(93)
+    E = Encoder().to(dev).eval()
+    E.quantizer.initial()
+    L = chunk // 300
+    x = 0.1 * torch.randn(N, 1, chunk, generator=torch.Generator().manual_seed(1)).to(dev)
+    xs = [x[i:i + 1].contiguous() for i in range(N)]
+    if half == "tx":
+        solo = [StreamSession(E, 1, chunk, graph=True, dtype=dtype) for _ in range(N)]
+        lock = StreamSession(E, N, chunk, graph=True, dtype=dtype)
+        pool = StreamPool(E, N, chunk, graph=True, dtype=dtype)
+        paths = {"solo": lambda: [S.quantize(S.encode(xi)) for S, xi in zip(solo, xs)],
+                 "lockstep": lambda: lock.quantize(lock.encode(x)),
+                 "pool": lambda: pool.quantize(pool.encode(all_slots, x)),
+                 "pool_k": lambda: pool.quantize(pool.encode(some_slots, x_some))}
+    else:
+        V = Vocoder(**configs.VOCODER_V1).to(dev).eval()
+        idx = E.quantize(E.encode(x))                   # (codebooks, N, frames)
+        idxs = [idx[:, i].contiguous() for i in range(N)]
+        solo = [VocoderSession(V, 1, L, graph=True, dtype=dtype) for _ in range(N)]
+        lock = VocoderSession(V, N, L, graph=True, dtype=dtype)
+        pool = VocoderPool(V, N, L, graph=True, dtype=dtype)
+        for S in solo + [lock, pool]:
+            S.lookup_generator = E
+        paths = {"solo": lambda: [S.decode(S.lookup(i)) for S, i in zip(solo, idxs)],
+                 "lockstep": lambda: lock.decode(lock.lookup(idx)),
+                 "pool": lambda: pool.decode(all_slots, pool.lookup(idx)),
+                 "pool_k": lambda: pool.decode(some_slots, pool.lookup(idx_some))}
+    all_slots = [pool.open() for _ in range(N)]
+    some_slots = all_slots[::N // active][:active]
+    x_some = x[some_slots].contiguous()
+    if half != "tx":
+        idx_some = idx[:, some_slots].contiguous()
+    stream = torch.cuda.current_stream(dev)
+    rec = {p: dict(host=[], gpu=[]) for p in paths}
+    for hop in range(warmup + hops):
+        for path, fn in paths.items():
+            _, h, g = _timed(fn, stream)
+            if hop >= warmup:
+                rec[path]["host"].append(h)
+                rec[path]["gpu"].append(g)
+    return dict(half=half, dtype=str(dtype).replace("torch.", ""), streams=N, active=active, chunk=chunk, hops=hops,
+                paths={p: {k: _stats(v) for k, v in r.items()} for p, r in rec.items()})
+
+
+class _no_state_copy:
+    """Inside the block a session's or a pool's launch list ends before its
+    commit / copy_slots launch, so a graph captured there lacks that node.  For
+    measurement only: such an object never advances its state."""
+
+    def __enter__(self):
+        from sel import streamops as SO
+        self.keep = SO.commit, SO.copy_slots
+        SO.commit = lambda pairs: None
+        SO.copy_slots = lambda pairs, src_slots, dst_slots, n: None
+
+    def __exit__(self, *exc):
+        from sel import streamops as SO
+        SO.commit, SO.copy_slots = self.keep
+
+
+def _graph_half(obj, half):
+    """The fixed-buffer launch list (sel.streaming._Half) of a session or pool:
+    its run() replays the graph without filling the input or staging a list."""
+    return obj._enc if half == "tx" else obj._dec
+
+
+def run_attribution_config(half, dtype, N, chunk, hops, warmup, dev):
+    """Where the pool's time over the lockstep session goes at N of N active
+    (`half` as run_pool_config).  The inputs are fixed, so the replays alone
+    compute the same hop every time."""
+    from models.autoencoder.AudioDec import StreamGenerator as Encoder
+    from models.vocoder.HiFiGAN import StreamGenerator as Vocoder
+    from sel import configs
+    from sel.streaming import StreamPool, StreamSession, VocoderPool, VocoderSession
+    torch.manual_seed(93)
+    E = Encoder().to(dev).eval()
+    E.quantizer.initial()
+    if half == "tx":
+        inp = 0.1 * torch.randn(N, 1, chunk, generator=torch.Generator().manual_seed(1)).to(dev)
+
+        def build():
+            return (StreamSession(E, N, chunk, graph=True, dtype=dtype),
+                    StreamPool(E, N, chunk, graph=True, dtype=dtype))
+
+        def full(obj, *slots):
+            return obj.encode(*slots, inp)
+    else:
+        V = Vocoder(**configs.VOCODER_V1).to(dev).eval()
+        inp = torch.randn(N, chunk // 300, 64, generator=torch.Generator().manual_seed(2)).to(dev)
+
+        def build():
+            return (VocoderSession(V, N, chunk // 300, graph=True, dtype=dtype),
+                    VocoderPool(V, N, chunk // 300, graph=True, dtype=dtype))
+
+        def full(obj, *slots):
+            return obj.decode(*slots, inp)
+    lock, pool = build()
+    with _no_state_copy():
+        lock0, pool0 = build()
+    for p in (pool, pool0):
+        slots = [p.open() for _ in range(N)]
+        full(p, slots)                  # leaves the full list staged for the bare replays
+    hl, hl0, hp, hp0 = (_graph_half(o, half) for o in (lock, lock0, pool, pool0))
+    paths = {"lock_replay_no_commit": hl0.run, "lock_replay": hl.run, "pool_replay_no_copy": hp0.run,
+             "pool_replay": hp.run, "lock_full": lambda: full(lock), "pool_full": lambda: full(pool, slots)}
+    stream = torch.cuda.current_stream(dev)
+    rec = {p: dict(host=[], gpu=[]) for p in paths}
+    for hop in range(warmup + hops):
+        for path, fn in paths.items():
+            _, h, g = _timed(fn, stream)
+            if hop >= warmup:
+                rec[path]["host"].append(h)
+                rec[path]["gpu"].append(g)
+    return dict(half=half, dtype=str(dtype).replace("torch.", ""), streams=N, chunk=chunk, hops=hops,
+                paths={p: {k: _stats(v) for k, v in r.items()} for p, r in rec.items()})
+
+
+def main_attribution(a, dev):
+    results = []
+    for dt in a.dtypes:
+        for half in ("tx", "rx_v1"):
+            r = run_attribution_config(half, getattr(torch, dt), a.streams, 300, a.hops, a.warmup, dev)
+            results.append(r)
+            print(json.dumps(r), flush=True)
+    label = {"lock_replay": "lockstep replay", "lock_replay_no_commit": "... without its commit launch",
+             "pool_replay_no_copy": "pool replay without its copy launch", "pool_replay": "pool replay",
+             "pool_full": "pool full call (staging, input fill, replay)", "lock_full": "lockstep full call"}
+    lines = ["| step (host ms med) | " + " | ".join(f"{r['half']} {r['dtype']}" for r in results) + " |",
+             "|---|" + "---|" * len(results)]
+    for path, lab in label.items():
+        lines.append(f"| {lab} | " + " | ".join(f"{r['paths'][path]['host']['med']:.3f}" for r in results) + " |")
+    for r in results:
+        m = {k: v["host"]["med"] for k, v in r["paths"].items()}
+        # staging: what the pool's call adds to its replay beyond the input fill the lockstep call has too
+        parts = dict(indirection=m["pool_replay_no_copy"] - m["lock_replay_no_commit"],
+                     staging=(m["pool_full"] - m["pool_replay"]) - (m["lock_full"] - m["lock_replay"]),
+                     copy=m["pool_replay"] - m["pool_replay_no_copy"],
+                     commit=m["lock_replay"] - m["lock_replay_no_commit"])
+        r["parts_host_ms"] = parts
+        lines.append(f"{r['half']} {r['dtype']}: indirection {parts['indirection']:.3f} ms, staging "
+                     f"{parts['staging']:.3f} ms, copy launch {parts['copy']:.3f} ms (commit {parts['commit']:.3f} ms)")
+    out = a.out or os.path.join(REPO, "profiles", "stream_pool_attribution")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out + ".json", "w") as f:
+        json.dump(results, f, indent=1)
+    with open(out + ".md", "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+def main_pool(a, dev):
+    results = []
+    for dt in a.dtypes:
+        for half in ("tx", "rx_v1"):
+            r = run_pool_config(half, getattr(torch, dt), a.streams, a.active, 300, a.hops, a.warmup, dev)
+            results.append(r)
+            print(json.dumps(r), flush=True)
+    label = {"solo": "(a) {n} solo batch=1 sessions", "lockstep": "(b) lockstep batch={n} session",
+             "pool": "(c) pool, {n} of {n} active", "pool_k": "(d) pool, {k} of {n} active"}
+    lines = ["| half | dtype | path | host ms med (p5-p95) | GPU ms med (p5-p95) |", "|---|---|---|---|---|"]
+    verdicts = []
+    for r in results:
+        for path, lab in label.items():
+            h, g = r["paths"][path]["host"], r["paths"][path]["gpu"]
+            lines.append(f"| {r['half']} | {r['dtype']} | {lab.format(n=r['streams'], k=r['active'])} | "
+                         f"{h['med']:.3f} ({h['p5']:.3f}-{h['p95']:.3f}) | "
+                         f"{g['med']:.3f} ({g['p5']:.3f}-{g['p95']:.3f}) |")
+        pa = {k: v["host"] for k, v in r["paths"].items()}
+        gain = pa["solo"]["med"] - pa["pool"]["med"]
+        spread = max(pa["solo"]["p95"] - pa["solo"]["p5"], pa["pool"]["p95"] - pa["pool"]["p5"])
+        verdicts.append(f"acceptance {r['half']} {r['dtype']}: solo {pa['solo']['med']:.3f} ms - pool "
+                        f"{pa['pool']['med']:.3f} ms = {gain:.3f} ms vs 5-95% band {spread:.3f} ms: "
+                        f"{'MET' if gain > spread else 'NOT MET'}; (c)/(b) = "
+                        f"{pa['pool']['med'] / pa['lockstep']['med']:.3f}, (d)/(c) = "
+                        f"{pa['pool_k']['med'] / pa['pool']['med']:.3f}, (a)/(c) = "
+                        f"{pa['solo']['med'] / pa['pool']['med']:.2f}")
+    out = a.out or os.path.join(REPO, "profiles", "stream_pool_bench")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out + ".json", "w") as f:
+        json.dump(results, f, indent=1)
+    with open(out + ".md", "w") as f:
+        f.write("\n".join(lines + [""] + verdicts) + "\n")
+    print("\n".join(lines + verdicts))
+
+
 def main_vocoder(a, dev):
     results = []
     for dec in a.decoder:
@@ -196,11 +408,23 @@ def main():
     ap.add_argument("--decoder", nargs="+", choices=["audiodec", "v0", "v1", "v2"], default=["audiodec"],
                     help="the receiver's decoder: the AudioDec generator (both halves, the default), or one or more "
                          "HiFi-GAN vocoders at full width (receiver half only; profiles/stream_bench_vocoder)")
+    ap.add_argument("--pool", action="store_true",
+                    help="independent streams: solo sessions, the lockstep session and the stream pool "
+                         "(profiles/stream_pool_bench)")
+    ap.add_argument("--streams", type=int, default=16, help="--pool: streams / pool capacity")
+    ap.add_argument("--active", type=int, default=4, help="--pool: active slots of the partly filled tick")
+    ap.add_argument("--attribution", action="store_true",
+                    help="with --pool: where the pool's time over the lockstep session goes "
+                         "(profiles/stream_pool_attribution)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("stream_bench: needs the GPU (no CPU fallback)")
     dev = torch.device("cuda:0")
+    if a.attribution and not a.pool:
+        sys.exit("stream_bench: --attribution goes with --pool")
+    if a.pool:
+        return main_attribution(a, dev) if a.attribution else main_pool(a, dev)
     if a.decoder != ["audiodec"]:
         if "audiodec" in a.decoder:
             sys.exit("stream_bench: --decoder audiodec cannot be combined with a vocoder")
