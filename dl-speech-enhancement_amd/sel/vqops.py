@@ -15,6 +15,13 @@ class ResidualVQFn(torch.autograd.Function):
         update needs beside the four outputs: the contiguous fp32 ``x`` the kernel
         read and the code histogram ``counts`` (S, K)."""
         L.need_device(x, embeds)
+        # the kernel reads embeds as fp32 (S, D, K) memory with x's D: anything
+        # else would be read past its end
+        if x.dim() != 2:
+            raise L.SelError(f"ResidualVQFn: x must be (N, D), got {tuple(x.shape)}")
+        if embeds.dim() != 3 or embeds.dtype != torch.float32 or embeds.shape[1] != x.shape[1]:
+            raise L.SelError(f"ResidualVQFn: embeds must be an fp32 (S, D, K) stack with D = {x.shape[1]}, got "
+                             f"{embeds.dtype} {tuple(embeds.shape)}")
         x = x.contiguous().float()
         embeds = embeds.contiguous()
         N, D = x.shape
