@@ -1,0 +1,369 @@
+// Residual VQ for a streaming hop (include/sel.h: sel_rvq_step,
+// sel_rvq_lookup_step): the quantizer and the codebook lookup as stateless,
+// capturable step launches on few rows -- a B = 1 hop has one row, a 16-stream
+// tick sixteen.  sel_rvq_fwd (vq.hip) is built for thousands of rows in 16-row
+// blocks and also produces the histogram, SSE, loss and perplexity of training.
+//
+// Quantize: one workgroup per row, threads over codes, the residual in LDS.
+// Per (row, stage, code) the arithmetic is k_rvq_fwd's: |r|^2 with lanes over d
+// and wave_sum, dot and |e_k|^2 as fmaf chains over d ascending from the same
+// loaded column, dist = (|r|^2 - 2 dot) + |e_k|^2, lowest index on ties, then
+// q = e_idx, qst = r + (q - r), r <- r - qst, zq += qst.  A row's bits depend on
+// the row alone, so any grouping of rows into blocks gives the same result.
+//   k_rvq_step_col: D = 64, K = 1024 (the product codebooks).  512 threads, two
+//     adjacent codes each (one 8-byte load per row d), the codes' 64-value
+//     columns in registers (128 VGPRs of the 256 a thread has at 2 waves per
+//     SIMD).  A column does not depend on the
+//     residual: the next stage's columns are requested as soon as this stage's
+//     dot products have consumed the registers, and are in flight while the
+//     argmin -> gather -> update chain of this stage resolves.
+//   k_rvq_step_any: every accepted shape.  256 threads, 4 codes per thread per
+//     pass of 1024 codes, columns read inside the d loop.
+// No atomics, no workspace; idx is written per stage, so S is unbounded.
+#include <algorithm>
+
+#include "sel_common.h"
+
+namespace sel {
+namespace vqstep {
+
+constexpr int MAXD = 256;
+constexpr int COL_D = 64, COL_K = 1024;  // k_rvq_step_col's shape
+constexpr int COL_T = 512;                // its threads: COL_K / COL_T codes each
+constexpr int ANY_T = 256, ANY_CPT = 4;  // k_rvq_step_any: threads, codes per thread per pass
+
+__device__ __forceinline__ bool better(float d, int k, float bd, int bk) {
+  return d < bd || (d == bd && k < bk);
+}
+
+__device__ __forceinline__ void wave_argmin(float& d0, int& k0) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float d1 = __shfl_xor(d0, o, 64);
+    const int k1 = __shfl_xor(k0, o, 64);
+    if (better(d1, k1, d0, k0)) {
+      d0 = d1;
+      k0 = k1;
+    }
+  }
+}
+
+// rows of this launch: all of them, or the first min(max(*n_active, 0), cap) samples
+__device__ __forceinline__ int64_t active_rows(const int32_t* n_active, int cap, int T, int64_t rows) {
+  return n_active ? int64_t(min(max(*n_active, 0), cap)) * T : rows;
+}
+
+// What both quantize kernels do once every thread holds its best (distance, code):
+// the block argmin (NW waves), then the first wave applies the pick to the row.
+// A row whose distances are all NaN keeps the initial 0x7fffffff: the pick is
+// forced to code 0 before anything is read through it.
+template <int NW>
+__device__ __forceinline__ void pick_and_update(float bd, int bk, int D, int K, const float* __restrict__ E,
+                                                float* res, float* acc, float* red_d, int* red_k,
+                                                int64_t* __restrict__ idx_out, int64_t idx_off) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  wave_argmin(bd, bk);
+  if (lane == 0) {
+    red_d[wave] = bd;
+    red_k[wave] = bk;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    float d0 = lane < NW ? red_d[lane] : __builtin_inff();
+    int k0 = lane < NW ? red_k[lane] : 0x7fffffff;
+    wave_argmin(d0, k0);
+    if (unsigned(k0) >= unsigned(K)) k0 = 0;
+    if (lane == 0) *idx_out = int64_t(k0) + idx_off;
+    for (int d = lane; d < D; d += 64) {
+      const float q = E[int64_t(d) * K + k0];
+      const float rv = res[d];
+      const float diff = q - rv;
+      const float qst = rv + diff;
+      res[d] = rv - qst;
+      acc[d] += qst;
+    }
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(COL_T) void k_rvq_step_col(const float* __restrict__ z, int64_t rows, int T,
+                                                        const float* __restrict__ embeds, int S,
+                                                        const int32_t* __restrict__ n_active, int cap, int flatten,
+                                                        int64_t* __restrict__ idx, float* __restrict__ zq) {
+  constexpr int D = COL_D, K = COL_K, NW = COL_T / 64, C = COL_K / COL_T;
+  __shared__ __align__(16) float res[D];
+  __shared__ float acc[D];
+  __shared__ float red_d[NW];
+  __shared__ int red_k[NW];
+  __shared__ float xn;
+  const int64_t row = blockIdx.x;
+  if (row >= active_rows(n_active, cap, T, rows)) return;  // block-uniform
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  // One stage's codebook as a buffer resource: a load is then one VGPR byte
+  // offset (the thread's code pair) plus a scalar offset (the row d) -- 64
+  // separate 64-bit addresses would cost as many registers as the columns.
+  auto load_cols = [&](int s, float (&e)[C][D]) {
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(embeds + int64_t(s) * D * K), 0, D * K * int(sizeof(float)), 0x00020000);
+#pragma unroll
+    for (int d = 0; d < D; ++d) {
+      const float2 v = __builtin_bit_cast(
+          float2, __builtin_amdgcn_raw_buffer_load_b64(rs, tid * C * int(sizeof(float)), d * K * int(sizeof(float)), 0));
+      e[0][d] = v.x;
+      e[1][d] = v.y;
+    }
+  };
+  static_assert(C == 2, "one 8-byte load per row d covers the thread's two adjacent codes");
+  float e[C][D];  // the columns of codes C * tid + j
+  load_cols(0, e);
+  if (tid < D) {
+    res[tid] = z[row * D + tid];
+    acc[tid] = 0.f;
+  }
+  __syncthreads();
+
+  for (int s = 0; s < S; ++s) {
+    const float* __restrict__ E = embeds + int64_t(s) * D * K;
+    if (wave == 0) {
+      float v = 0.f;
+      v = fmaf(res[lane], res[lane], v);
+      v = wave_sum(v);
+      if (lane == 0) xn = v;
+    }
+    float dot[C], en[C];
+#pragma unroll
+    for (int j = 0; j < C; ++j) dot[j] = en[j] = 0.f;
+#pragma unroll
+    for (int d4 = 0; d4 < D; d4 += 4) {
+      const float4 r4 = *reinterpret_cast<const float4*>(res + d4);
+      const float rr[4] = {r4.x, r4.y, r4.z, r4.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < C; ++j) {
+          en[j] = fmaf(e[j][d4 + i], e[j][d4 + i], en[j]);
+          dot[j] = fmaf(rr[i], e[j][d4 + i], dot[j]);
+        }
+    }
+    // the registers are free: the next stage's columns, in flight during the pick
+    // (the empty asm pins the finished sums here: the compiler otherwise sinks
+    // the fmaf chains below the loads, towards their use after the barrier, and
+    // both stages' columns are live at once)
+#pragma unroll
+    for (int j = 0; j < C; ++j) asm volatile("" : "+v"(dot[j]), "+v"(en[j]) : : "memory");
+    if (s + 1 < S) load_cols(s + 1, e);
+    __syncthreads();
+    float bd = __builtin_inff();
+    int bk = 0x7fffffff;
+#pragma unroll
+    for (int j = 0; j < C; ++j) {  // ascending codes
+      const float dist = (xn - 2.f * dot[j]) + en[j];
+      if (better(dist, C * tid + j, bd, bk)) {
+        bd = dist;
+        bk = C * tid + j;
+      }
+    }
+    pick_and_update<NW>(bd, bk, D, K, E, res, acc, red_d, red_k, idx + int64_t(s) * rows + row,
+                        flatten ? int64_t(s) * K : 0);
+  }
+  if (zq && tid < D) zq[row * D + tid] = acc[tid];
+}
+
+__global__ __launch_bounds__(ANY_T) void k_rvq_step_any(const float* __restrict__ z, int64_t rows, int T, int D,
+                                                        const float* __restrict__ embeds, int S, int K,
+                                                        const int32_t* __restrict__ n_active, int cap, int flatten,
+                                                        int64_t* __restrict__ idx, float* __restrict__ zq) {
+  constexpr int NW = ANY_T / 64;
+  __shared__ float res[MAXD];
+  __shared__ float acc[MAXD];
+  __shared__ float red_d[NW];
+  __shared__ int red_k[NW];
+  __shared__ float xn;
+  const int64_t row = blockIdx.x;
+  if (row >= active_rows(n_active, cap, T, rows)) return;  // block-uniform
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int d = tid; d < D; d += ANY_T) {
+    res[d] = z[row * D + d];
+    acc[d] = 0.f;
+  }
+  __syncthreads();
+
+  for (int s = 0; s < S; ++s) {
+    const float* __restrict__ E = embeds + int64_t(s) * D * K;
+    if (wave == 0) {
+      float v = 0.f;
+      for (int d = lane; d < D; d += 64) v = fmaf(res[d], res[d], v);
+      v = wave_sum(v);
+      if (lane == 0) xn = v;
+    }
+    __syncthreads();
+    const float x2 = xn;
+    float bd = __builtin_inff();
+    int bk = 0x7fffffff;
+    for (int64_t kb = 0; kb < K; kb += ANY_T * ANY_CPT) {
+      float dot[ANY_CPT], en[ANY_CPT];
+      int64_t col[ANY_CPT];  // a dead code reads column 0 and is not scored
+#pragma unroll
+      for (int j = 0; j < ANY_CPT; ++j) {
+        dot[j] = en[j] = 0.f;
+        const int64_t k = kb + tid + j * ANY_T;
+        col[j] = k < K ? k : 0;
+      }
+      for (int d = 0; d < D; ++d) {
+        const float rv = res[d];
+        const float* __restrict__ Ed = E + int64_t(d) * K;
+#pragma unroll
+        for (int j = 0; j < ANY_CPT; ++j) {
+          const float ev = Ed[col[j]];
+          en[j] = fmaf(ev, ev, en[j]);
+          dot[j] = fmaf(rv, ev, dot[j]);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < ANY_CPT; ++j) {
+        const int64_t k = kb + tid + j * ANY_T;
+        if (k >= K) continue;
+        const float dist = (x2 - 2.f * dot[j]) + en[j];
+        if (better(dist, int(k), bd, bk)) {
+          bd = dist;
+          bk = int(k);
+        }
+      }
+    }
+    pick_and_update<NW>(bd, bk, D, K, E, res, acc, red_d, red_k, idx + int64_t(s) * rows + row,
+                        flatten ? int64_t(s) * K : 0);
+  }
+  if (zq)
+    for (int d = tid; d < D; d += ANY_T) zq[row * D + d] = acc[d];
+}
+
+// ---- lookup: out[row] = sum over stages of codebook[idx[s, row]], stages ascending ----
+template <typename TO> __device__ __forceinline__ TO to_out(float v);
+template <> __device__ __forceinline__ float to_out<float>(float v) { return v; }
+template <> __device__ __forceinline__ __bf16 to_out<__bf16>(float v) { return static_cast<__bf16>(v); }  // RNE
+
+struct LookupArgs {
+  const int64_t* idx;
+  const float* codebook;
+  const float* mean;
+  const float* scale;
+  const int32_t* n_active;
+  int64_t rows, ncodes;
+  int T, S, D, cap;
+};
+
+constexpr int LK_T = 256;
+
+// V = 4: one thread per 4 channels (D % 4 == 0, 16-byte aligned operands); V = 1: per channel
+template <typename TO, int V>
+__global__ __launch_bounds__(LK_T) void k_rvq_lookup_step(LookupArgs a, TO* __restrict__ out) {
+  const int per_row = a.D / V;
+  const int64_t live = active_rows(a.n_active, a.cap, a.T, a.rows);
+  const int64_t i0 = int64_t(blockIdx.x) * LK_T;
+  if (i0 / per_row >= live) return;  // block-uniform: the whole block lies beyond the active rows
+  const int64_t i = i0 + threadIdx.x;
+  const int64_t row = i / per_row;
+  if (row >= live) return;
+  const int d0 = int(i % per_row) * V;
+  float acc[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) acc[j] = 0.f;
+  bool first = true;
+  for (int s = 0; s < a.S; ++s) {
+    const int64_t id = a.idx[int64_t(s) * a.rows + row];
+    if (id < 0 || id >= a.ncodes) continue;  // contributes zero; nothing is read through it
+    const float* __restrict__ c = a.codebook + id * a.D + d0;
+    float v[V];
+    if constexpr (V == 4) {
+      const float4 c4 = *reinterpret_cast<const float4*>(c);
+      v[0] = c4.x; v[1] = c4.y; v[2] = c4.z; v[3] = c4.w;
+    } else {
+      v[0] = c[0];
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc[j] = first ? v[j] : __fadd_rn(acc[j], v[j]);
+    first = false;
+  }
+  if (a.mean) {
+#pragma unroll
+    for (int j = 0; j < V; ++j) acc[j] = __fdiv_rn(__fsub_rn(acc[j], a.mean[d0 + j]), a.scale[d0 + j]);
+  }
+  TO* __restrict__ o = out + row * a.D + d0;
+  if constexpr (V == 4 && sizeof(TO) == 4) {
+    *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+  } else if constexpr (V == 4) {
+    union {
+      __bf16 h[4];
+      uint2 u;
+    } p;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p.h[j] = to_out<__bf16>(acc[j]);
+    *reinterpret_cast<uint2*>(o) = p.u;
+  } else {
+    o[0] = to_out<TO>(acc[0]);
+  }
+}
+
+}  // namespace vqstep
+}  // namespace sel
+
+using namespace sel;
+using namespace sel::vqstep;
+
+extern "C" {
+
+int sel_rvq_step(const float* z, int rows, int rows_per_sample, int D, const float* embeds, int S, int K,
+                 const int32_t* n_active, int flatten, int64_t* idx, float* zq, sel_stream_t stream) {
+  SEL_REQUIRE(rows >= 1 && rows_per_sample >= 1 && rows % rows_per_sample == 0, SEL_ERR_ARG,
+              "sel_rvq_step: rows (%d) must be a positive multiple of rows_per_sample (%d)", rows, rows_per_sample);
+  SEL_REQUIRE(D > 0 && D <= MAXD && K > 0 && S > 0, SEL_ERR_ARG, "sel_rvq_step: bad shape D=%d (1..%d) K=%d S=%d", D,
+              MAXD, K, S);
+  SEL_REQUIRE(z && embeds && idx, SEL_ERR_ARG, "sel_rvq_step: null z / embeds / idx");
+  SEL_REQUIRE(zq != z, SEL_ERR_ARG, "sel_rvq_step: zq aliases z");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int cap = rows / rows_per_sample;
+  if (D == COL_D && K == COL_K)
+    hipLaunchKernelGGL(k_rvq_step_col, dim3(unsigned(rows)), dim3(COL_T), 0, s, z, int64_t(rows), rows_per_sample,
+                       embeds, S, n_active, cap, flatten, idx, zq);
+  else
+    hipLaunchKernelGGL(k_rvq_step_any, dim3(unsigned(rows)), dim3(ANY_T), 0, s, z, int64_t(rows), rows_per_sample, D,
+                       embeds, S, K, n_active, cap, flatten, idx, zq);
+  SEL_LAUNCH_CHECK();
+  return SEL_OK;
+}
+
+int sel_rvq_lookup_step(const int64_t* idx, int rows, int rows_per_sample, int S, int64_t ncodes, int D,
+                        const float* codebook, const float* mean, const float* scale, const int32_t* n_active,
+                        int out_dtype, void* out, sel_stream_t stream) {
+  SEL_REQUIRE(rows >= 1 && rows_per_sample >= 1 && rows % rows_per_sample == 0, SEL_ERR_ARG,
+              "sel_rvq_lookup_step: rows (%d) must be a positive multiple of rows_per_sample (%d)", rows,
+              rows_per_sample);
+  SEL_REQUIRE(S > 0 && D > 0 && ncodes > 0, SEL_ERR_ARG, "sel_rvq_lookup_step: bad shape S=%d D=%d ncodes=%lld", S, D,
+              (long long)ncodes);
+  SEL_REQUIRE(ncodes <= (int64_t(1) << 40) / D, SEL_ERR_ARG, "sel_rvq_lookup_step: codebook of %lld x %d out of range",
+              (long long)ncodes, D);
+  SEL_REQUIRE(idx && codebook && out, SEL_ERR_ARG, "sel_rvq_lookup_step: null idx / codebook / out");
+  SEL_REQUIRE((mean == nullptr) == (scale == nullptr), SEL_ERR_ARG,
+              "sel_rvq_lookup_step: mean and scale come together or not at all");
+  SEL_REQUIRE(out_dtype == SEL_F32 || out_dtype == SEL_BF16, SEL_ERR_ARG, "sel_rvq_lookup_step: out_dtype must be fp32 or bf16");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  const bool vec = D % 4 == 0 && al16(codebook) && al16(out) && al16(mean) && al16(scale);
+  LookupArgs a{idx, codebook, mean, scale, n_active, int64_t(rows), ncodes, rows_per_sample, S, D,
+               rows / rows_per_sample};
+  const int64_t threads = int64_t(rows) * (vec ? D / 4 : D);
+  SEL_REQUIRE(threads / LK_T < (int64_t(1) << 31) - 1, SEL_ERR_ARG, "sel_rvq_lookup_step: rows * D out of range");
+  const dim3 grid(unsigned((threads + LK_T - 1) / LK_T));
+  if (out_dtype == SEL_F32) {
+    if (vec) hipLaunchKernelGGL((k_rvq_lookup_step<float, 4>), grid, dim3(LK_T), 0, s, a, static_cast<float*>(out));
+    else hipLaunchKernelGGL((k_rvq_lookup_step<float, 1>), grid, dim3(LK_T), 0, s, a, static_cast<float*>(out));
+  } else {
+    if (vec) hipLaunchKernelGGL((k_rvq_lookup_step<__bf16, 4>), grid, dim3(LK_T), 0, s, a, static_cast<__bf16*>(out));
+    else hipLaunchKernelGGL((k_rvq_lookup_step<__bf16, 1>), grid, dim3(LK_T), 0, s, a, static_cast<__bf16*>(out));
+  }
+  SEL_LAUNCH_CHECK();
+  return SEL_OK;
+}
+
+}  // extern "C"

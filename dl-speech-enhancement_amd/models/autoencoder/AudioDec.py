@@ -99,18 +99,27 @@ class StreamGenerator(Generator):
     def decode(self, zq):
         return self.decoder.decode(zq.transpose(2, 1))
 
-    def session(self, batch=1, chunk=300, graph=True):
+    def session(self, batch=1, chunk=300, graph=True, codes=False):
         """An opt-in sel.streaming.StreamSession over this generator: fixed state,
-        one step launch per layer, each hop replayed as a graph."""
+        one step launch per layer, each hop replayed as a graph.  ``codes=True``
+        also calls ``enable_codes()``: ``transmit`` / ``receive`` with the
+        quantizer and the lookup inside the hop."""
         from sel.streaming import StreamSession
-        return StreamSession(self, batch, chunk, graph)
+        s = StreamSession(self, batch, chunk, graph)
+        if codes:
+            s.enable_codes()
+        return s
 
-    def pool(self, capacity, chunk=300, graph=True, dtype=None):
+    def pool(self, capacity, chunk=300, graph=True, dtype=None, codes=False):
         """An opt-in sel.streaming.StreamPool over this generator: `capacity`
         independent streams that open, close and tick on their own, one batched
-        hop per tick over the active ones."""
+        hop per tick over the active ones.  ``codes=True`` also calls
+        ``enable_codes()``."""
         from sel.streaming import StreamPool
-        return StreamPool(self, capacity, chunk, graph, dtype)
+        p = StreamPool(self, capacity, chunk, graph, dtype)
+        if codes:
+            p.enable_codes()
+        return p
 
     def reset_buffer(self):
         """Zero every causal layer's pad_buffer (AudioDec.py:185-191)."""

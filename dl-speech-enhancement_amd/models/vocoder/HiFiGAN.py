@@ -225,17 +225,27 @@ class StreamGenerator(Generator):
                              out_dtype=torch.float32)
         return x.transpose(1, 2)
 
-    def session(self, batch=1, frames=1, graph=True):
+    def session(self, batch=1, frames=1, graph=True, codes=False):
         """An opt-in sel.streaming.VocoderSession over this generator: fixed state,
-        one grouped step launch per conv, each hop of `frames` frames replayed as a graph."""
+        one grouped step launch per conv, each hop of `frames` frames replayed as a graph.
+        ``codes=True`` also calls ``enable_codes()``; a vocoder has no codebooks of
+        its own, so ``receive`` works once ``enable_codes(lookup_generator)`` has
+        been given the encoder's generator."""
         from sel.streaming import VocoderSession
-        return VocoderSession(self, batch, frames, graph)
+        s = VocoderSession(self, batch, frames, graph)
+        if codes:
+            s.enable_codes()
+        return s
 
-    def pool(self, capacity, frames=1, graph=True, dtype=None):
+    def pool(self, capacity, frames=1, graph=True, dtype=None, codes=False):
         """An opt-in sel.streaming.VocoderPool over this generator: `capacity`
-        independent streams, one batched hop per tick over the active ones."""
+        independent streams, one batched hop per tick over the active ones.
+        ``codes=True`` as in ``session``."""
         from sel.streaming import VocoderPool
-        return VocoderPool(self, capacity, frames, graph, dtype)
+        p = VocoderPool(self, capacity, frames, graph, dtype)
+        if codes:
+            p.enable_codes()
+        return p
 
     def reset_buffer(self):
         """Zero every streaming pad_buffer."""

@@ -24,7 +24,16 @@ a fixed number of slots, each holding one stream's carries, and per tick one
 batched hop over whichever slots have a hop ready, on the slot-indexed step
 kernels (``sel_conv_step_pool`` / ``sel_hfg_conv_step_pool``); the active set is
 device data, so one captured graph serves every tick.
+
+``enable_codes()`` on any of the four puts the quantizer behind the
+transmitter's hop and the codebook lookup in front of the receiver's, as
+stateless step launches (``sel_rvq_step`` / ``sel_rvq_lookup_step``,
+csrc/vq_step.hip) in second graphs beside the existing ones: ``transmit`` is
+then one replay from samples to code indices, ``receive`` one from code
+indices to samples.
 """
+import functools
+
 import torch
 
 from . import _lib as L
@@ -95,8 +104,127 @@ class _Half:
             if c is not None:
                 c.zero_()
 
+    # ---- code indices inside the hop (enable_codes) --------------------------------
+    pre = post = codes_graph = idx = None
 
-class StreamSession:
+    def add_codes(self, idx, pre=None, post=None):
+        """Extend the hop by a stateless launch in front of it (``pre``: the lookup
+        into ``inp``) or behind it (``post``: the quantizer on ``outs[-1]``), as a
+        second launch list beside ``launch`` -- and, for a captured half, a second
+        graph beside ``graph``.  Only the new launch is warmed up eagerly (it has
+        no state); the capture itself executes nothing, so no carry moves."""
+        self.idx, self.pre, self.post = idx, pre, post
+        self.codes_graph = None
+        if self.graph is not None:
+            (pre or post)()
+            torch.cuda.synchronize(self.inp.device)
+            self.codes_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.codes_graph):
+                self.launch_codes()
+
+    def launch_codes(self):
+        if self.pre is not None:
+            self.pre()
+        self.launch()
+        if self.post is not None:
+            self.post()
+
+    def run_codes(self):
+        if self.codes_graph is not None:
+            self.codes_graph.replay()
+        else:
+            self.launch_codes()
+        return self.outs[-1]
+
+
+def _fill_idx(dst, idx, what):
+    """idx (S, [batch,] frames) int64 -> the fixed (S, rows) buffer (or its first rows)."""
+    L.need_device(idx)
+    if idx.dtype != torch.int64 or idx.dim() < 2 or idx.shape[0] != dst.shape[0] or idx.numel() != dst.numel():
+        raise L.SelError(f"sel: {what} takes int64 indices of {dst.shape[0]} codebooks x {dst.shape[1]} frames, "
+                         f"got {idx.dtype} {tuple(idx.shape)}")
+    dst.copy_(idx.reshape(dst.shape))
+
+
+class _CodesMixin:
+    """``enable_codes`` / ``transmit`` / ``receive`` of sessions and pools: the
+    quantizer behind the transmitter's hop and the codebook lookup in front of
+    the receiver's, inside the hop's launch list (csrc/vq_step.hip)."""
+    _tx = _rx = None          # the halves that carry codes once enable_codes ran
+    _codes_enabled = False
+
+    @torch.no_grad()
+    def enable_codes(self, lookup_generator=None):
+        """Put ``quantize`` behind ``encode`` and ``lookup`` in front of ``decode``:
+        afterwards ``transmit`` is one replay from samples to code indices and
+        ``receive`` one replay from code indices to samples.
+
+        The transmitter half (an AudioDec session / pool with PQC) snapshots its
+        own generator's codebook stack (S, D, K); the receiver half snapshots the
+        flat (S*K, D) codebook of ``lookup_generator`` (default:
+        ``self.lookup_generator``; none known: no receiver half) and, for a
+        vocoder with ``stats``, its mean / scale.  The snapshots are private fp32
+        copies taken once, like the packed weights: call ``enable_codes`` again
+        after the codebooks change.  With ``graph=True`` the extended hops are
+        captured as NEW graphs beside the existing ones; ``encode`` / ``decode`` /
+        ``quantize`` / ``lookup`` keep their graphs and their bits.  No carry and
+        no template row changes (safe after ``load_state()``)."""
+        dev = self._dec.inp.device
+        frames = self.plan.frames
+        self._tx = self._rx = None
+        enc = getattr(self, "_enc", None)
+        if enc is not None and self.plan.pqc:
+            rvq = self.generator.quantizer.codebook
+            stack = torch.stack([l.embed.detach() for l in rvq.layers]).to(dev, torch.float32).contiguous().clone()
+            z = enc.outs[-1]
+            if z.dtype != torch.float32 or z.shape[1] != stack.shape[1]:
+                raise L.SelError(f"sel: encode's output rows {z.dtype} {tuple(z.shape)} are not the fp32 code vectors "
+                                 f"of a (S, D, K) = {tuple(stack.shape)} quantizer")
+            idx = torch.zeros((stack.shape[0], z.shape[0]), dtype=torch.int64, device=dev)
+            count = getattr(enc, "n_active", None)
+            self._prepare_codes(enc)
+            enc.add_codes(idx, post=functools.partial(SO.rvq_step, z, stack, idx, frames, count, True))
+            self._tx = enc
+        lg = lookup_generator if lookup_generator is not None else self.lookup_generator
+        dec = self._dec
+        if lg is not None and (enc is None or self.plan.pqc):
+            rvq = lg.quantizer.codebook
+            if not hasattr(rvq, "codebook_size"):
+                lg.quantizer.initial()
+            flat = rvq.codebook.detach().to(dev, torch.float32).contiguous().clone()
+            S = len(rvq.layers)
+            if dec.inp.shape[-1] != flat.shape[1]:
+                raise L.SelError(f"sel: the lookup codebook has {flat.shape[1]} channels, decode takes "
+                                 f"{dec.inp.shape[-1]}")
+            idx = torch.zeros((S, dec.inp.shape[0] * frames), dtype=torch.int64, device=dev)
+            mean = scale = None
+            if getattr(self.generator, "norm", False):
+                mean = self.generator.mean.detach().to(dev, torch.float32).contiguous().clone()
+                scale = self.generator.scale.detach().to(dev, torch.float32).contiguous().clone()
+            count = getattr(dec, "n_active", None)
+            self._prepare_codes(dec)
+            dec.add_codes(idx, pre=functools.partial(SO.rvq_lookup_step, idx, flat, dec.inp, frames, mean, scale, count))
+            self._rx = dec
+        self._codes_enabled = True
+
+    def _prepare_codes(self, half):
+        """Before a half's new launch is warmed up and captured (pools: no active stream)."""
+
+    def _codes_half(self, which):
+        if not self._codes_enabled:
+            raise L.SelError(f"sel: {which} needs enable_codes() first")
+        if which == "transmit":
+            if self._tx is None:
+                raise L.SelError("sel: transmit needs a transmitter with PQC: without it (or on a vocoder) encode's "
+                                 "output is not the projector's fp32 code vector")
+            return self._tx
+        if self._rx is None:
+            raise L.SelError("sel: receive knows no lookup codebook: set lookup_generator (the generator whose "
+                             "codebooks decode the indices) and call enable_codes() again")
+        return self._rx
+
+
+class StreamSession(_CodesMixin):
     """One streaming endpoint state: ``batch`` parallel streams, ``chunk`` samples per hop.
 
     ``encode(x) -> z``, ``quantize(z) -> idx``, ``lookup(idx) -> zq`` and
@@ -182,6 +310,30 @@ class StreamSession:
         self._dec.inp.copy_(src)
         return self._dec.run().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
 
+    # ---- the same with the code indices inside the hop (after enable_codes) -----
+    @torch.no_grad()
+    def transmit(self, x):
+        """x (batch, in_channels, chunk) -> flattened code indices, int64, what
+        ``quantize(encode(x))`` returns: one replay.  A VIEW of a fixed buffer,
+        valid until the next ``transmit``."""
+        half = self._codes_half("transmit")
+        pl = self.plan
+        L.need_device(x)
+        if tuple(x.shape) != (pl.batch, pl.in_channels, pl.chunk):
+            raise L.SelError(f"sel: session transmit takes {(pl.batch, pl.in_channels, pl.chunk)}, got {tuple(x.shape)}")
+        half.inp.copy_(x.transpose(1, 2))
+        half.run_codes()
+        return half.idx.view(-1, pl.batch, pl.frames).squeeze(1)
+
+    @torch.no_grad()
+    def receive(self, idx):
+        """The indices ``transmit`` / ``quantize`` return -> y, what
+        ``decode(lookup(idx))`` returns (the codes summed in stage order): one replay."""
+        half = self._codes_half("receive")
+        pl = self.plan
+        _fill_idx(half.idx, idx, "session receive")
+        return half.run_codes().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
+
     # ---- state ------------------------------------------------------------------
     def _layers(self):
         for half in (self._enc, self._dec):
@@ -261,7 +413,7 @@ class _VocoderHalf(_Half):
         SO.commit(self.pairs)
 
 
-class VocoderSession:
+class VocoderSession(_CodesMixin):
     """The receiver's streaming state for a HiFi-GAN vocoder ``StreamGenerator``:
     ``batch`` parallel streams, ``frames`` code frames per hop.
 
@@ -321,6 +473,10 @@ class VocoderSession:
             raise L.SelError(f"sel: session decode takes {(pl.batch, pl.frames, pl.in_channels)}, got {tuple(c.shape)}")
         self._dec.inp.copy_(self.generator.decode_norm(c))
         return self._dec.run().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
+
+    # after enable_codes(): lookup, decode_norm and decode as one replay (transmit: always a SelError)
+    transmit = StreamSession.transmit
+    receive = StreamSession.receive
 
     # ---- state ------------------------------------------------------------------
     def _layers(self):
@@ -425,7 +581,7 @@ class _VocoderPoolHalf(_PoolMixin, _VocoderHalf):
         self._make_pool(capacity, device)
 
 
-class _PoolBase:
+class _PoolBase(_CodesMixin):
     """Slots, the template row, staging and opening: shared by StreamPool and VocoderPool."""
 
     def _init_pool(self, capacity, halves, device):
@@ -452,6 +608,39 @@ class _PoolBase:
         slots = self.table.check(slots)
         self._stager.stage(half.ctl, [len(slots)] + slots)
         return len(slots)
+
+    def _prepare_codes(self, half):
+        # n_active = 0: the warm-up launch and the capture touch no row
+        if half.graph is not None:
+            half.ctl.zero_()
+
+    @torch.no_grad()
+    def transmit(self, slots, x):
+        """x (n, in_channels, chunk) for the n listed slots -> flattened code indices
+        (codebooks, n, frames), what ``quantize(encode(slots, x))`` returns: one
+        replay.  A VIEW of a fixed buffer, valid until the next ``transmit``."""
+        half = self._codes_half("transmit")
+        pl = self.plan
+        L.need_device(x)
+        if tuple(x.shape) != (len(slots), pl.in_channels, pl.chunk):
+            raise L.SelError(f"sel: pool transmit takes {(len(slots), pl.in_channels, pl.chunk)} for {len(slots)} "
+                             f"slots, got {tuple(x.shape)}")
+        n = self._stage(half, slots)
+        half.inp[:n].copy_(x.transpose(1, 2))
+        half.run_codes()
+        return half.idx.view(-1, self.capacity, pl.frames)[:, :n]
+
+    @torch.no_grad()
+    def receive(self, slots, idx):
+        """idx (codebooks, n, frames), what ``transmit`` / ``quantize`` return, for the
+        n listed slots -> y (n, out_channels, samples), what ``decode(slots,
+        lookup(idx))`` returns (the codes summed in stage order): one replay."""
+        half = self._codes_half("receive")
+        pl = self.plan
+        n = self._stage(half, slots)
+        _fill_idx(half.idx[:, :n * pl.frames], idx, f"pool receive for {n} slots")
+        out = half.run_codes()
+        return out.view(self.capacity, pl.out_samples, pl.out_channels)[:n].transpose(1, 2)
 
     def _layers(self):
         for half in self._halves:

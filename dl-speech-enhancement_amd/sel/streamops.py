@@ -18,6 +18,10 @@ tests/test_vocoder_plan_host.py executes its plans against the reference goldens
 ``conv_step_pool`` / ``hfg_conv_step_pool`` / ``copy_slots`` bind the
 slot-indexed forms for stream pools (``sel.streaming.StreamPool``), and
 ``SlotTable`` is the host-side record of which slots are open.
+
+``rvq_step`` / ``rvq_lookup_step`` bind the quantizer and the codebook lookup of a
+hop as stateless step launches (csrc/vq_step.hip), which
+``sel.streaming``'s ``enable_codes`` puts inside the hop's launch list.
 """
 import ctypes
 from dataclasses import dataclass
@@ -216,6 +220,72 @@ def copy_slots(pairs, src_slots, dst_slots, n):
                                     for s, d in pairs])
     L.call("sel_stream_copy_slots", ctypes.cast(jobs, ctypes.c_void_p), len(pairs), nslots, L.ptr(src_slots),
            L.ptr(dst_slots), cap, L.ptr(n), L.stream())
+
+
+# ---- the residual VQ of a hop as step launches (include/sel.h sel_rvq_step) --------------------
+def _count_operand(what, n_active):
+    if n_active is not None and (n_active.dtype != torch.int32 or not n_active.is_contiguous()
+                                 or n_active.numel() < 1):
+        raise L.SelError(f"sel: {what} takes a contiguous int32 device tensor for n_active")
+
+
+def rvq_step(z, embeds, idx, rows_per_sample=1, n_active=None, flatten=True, zq=None):
+    """One sel_rvq_step launch on the current stream: z (rows, D) fp32 rows ->
+    idx (S, rows) int64 picks (flatten: + s*K, ids into the flat codebook) and,
+    when given, zq (rows, D) fp32.  embeds: the (S, D, K) fp32 codebook stack.
+    n_active (1 int32, DEVICE) makes the first n_active * rows_per_sample rows
+    the only ones read and written.  Nothing is allocated.  Returns idx."""
+    L.need_device(z, embeds, idx, n_active, zq)
+    if embeds.dim() != 3 or embeds.dtype != torch.float32 or not embeds.is_contiguous():
+        raise L.SelError(f"sel: rvq_step takes a contiguous fp32 (S, D, K) stack, got {embeds.dtype} "
+                         f"{tuple(embeds.shape)}")
+    S, D, K = embeds.shape
+    if z.dim() != 2 or z.shape[1] != D or z.dtype != torch.float32 or not z.is_contiguous():
+        raise L.SelError(f"sel: rvq_step takes contiguous fp32 rows (rows, {D}), got {z.dtype} {tuple(z.shape)}")
+    rows = z.shape[0]
+    if idx.dtype != torch.int64 or not idx.is_contiguous() or tuple(idx.shape) != (S, rows):
+        raise L.SelError(f"sel: rvq_step writes a contiguous int64 idx of shape {(S, rows)}, got {idx.dtype} "
+                         f"{tuple(idx.shape)}")
+    if zq is not None and (zq.dtype != torch.float32 or not zq.is_contiguous() or zq.shape != z.shape):
+        raise L.SelError(f"sel: rvq_step writes a contiguous fp32 zq of shape {tuple(z.shape)}")
+    if rows_per_sample < 1 or rows % rows_per_sample:
+        raise L.SelError(f"sel: rvq_step rows ({rows}) is not a multiple of rows_per_sample ({rows_per_sample})")
+    _count_operand("rvq_step", n_active)
+    L.call("sel_rvq_step", L.ptr(z), rows, rows_per_sample, D, L.ptr(embeds), S, K, L.ptr(n_active),
+           int(bool(flatten)), L.ptr(idx), L.ptr(zq), L.stream())
+    return idx
+
+
+def rvq_lookup_step(idx, codebook, out, rows_per_sample=1, mean=None, scale=None, n_active=None):
+    """One sel_rvq_lookup_step launch on the current stream: idx (S, rows) int64
+    ids into codebook (ncodes, D) fp32 (ResidualVQ.initial()'s flat layout) ->
+    out (rows, D) fp32 or bf16: the codes summed in fp32 in ascending stage order,
+    then (acc - mean) / scale when both are given (D fp32 each), then rounded to
+    out's dtype.  n_active as in rvq_step.  Nothing is allocated.  Returns out."""
+    L.need_device(idx, codebook, out, mean, scale, n_active)
+    if codebook.dim() != 2 or codebook.dtype != torch.float32 or not codebook.is_contiguous():
+        raise L.SelError(f"sel: rvq_lookup_step takes a contiguous fp32 (ncodes, D) codebook, got {codebook.dtype} "
+                         f"{tuple(codebook.shape)}")
+    ncodes, D = codebook.shape
+    if idx.dim() != 2 or idx.dtype != torch.int64 or not idx.is_contiguous():
+        raise L.SelError(f"sel: rvq_lookup_step takes a contiguous int64 idx (S, rows), got {idx.dtype} "
+                         f"{tuple(idx.shape)}")
+    S, rows = idx.shape
+    if out.dtype not in (torch.float32, torch.bfloat16) or not out.is_contiguous() or out.numel() != rows * D:
+        raise L.SelError(f"sel: rvq_lookup_step writes {rows} contiguous fp32 / bf16 rows of {D}, got {out.dtype} "
+                         f"{tuple(out.shape)}")
+    if (mean is None) != (scale is None):
+        raise L.SelError("sel: rvq_lookup_step takes mean and scale together or not at all")
+    for t in (mean, scale):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != D):
+            raise L.SelError(f"sel: rvq_lookup_step takes contiguous fp32 mean / scale of {D} elements")
+    if rows_per_sample < 1 or rows % rows_per_sample:
+        raise L.SelError(f"sel: rvq_lookup_step rows ({rows}) is not a multiple of rows_per_sample "
+                         f"({rows_per_sample})")
+    _count_operand("rvq_lookup_step", n_active)
+    L.call("sel_rvq_lookup_step", L.ptr(idx), rows, rows_per_sample, S, ncodes, D, L.ptr(codebook), L.ptr(mean),
+           L.ptr(scale), L.ptr(n_active), CO._code(out.dtype), L.ptr(out), L.stream())
+    return out
 
 
 @dataclass(frozen=True)

@@ -47,14 +47,17 @@ class AudioDec(AudioCodec):
             return _load_generator(generator_hifigan, config, checkpoint)
         raise NotImplementedError(f"Decoder {config['model_type']} is not supported!")
 
-    def open_session(self, batch=1, chunk=300, graph=True):
+    def open_session(self, batch=1, chunk=300, graph=True, codes=False):
         """(tx, rx) streaming sessions, warmed up as load_transmitter / load_receiver
         left the models: ``tx.encode -> tx.quantize`` on the transmitter,
         ``rx.lookup -> rx.decode`` on the receiver.  The receiver's session runs
         the lookup on rx_encoder's codebook and the decode on the decoder: a
         ``StreamSession`` for an AudioDec generator, a ``VocoderSession`` of
         ``chunk / hop`` frames per hop for the HiFi-GAN vocoder decoder (hop =
-        the product of its upsample scales)."""
+        the product of its upsample scales).  ``codes=True`` also calls
+        ``enable_codes()`` on both (after the warm-up state is loaded and the
+        receiver knows rx_encoder): ``tx.transmit`` / ``rx.receive`` then run the
+        quantizer and the lookup inside the hop."""
         from sel.streaming import StreamSession, VocoderSession
         if self.tx_encoder is None or self.rx_encoder is None or self.decoder is None:
             raise RuntimeError("open_session: call load_transmitter and load_receiver first")
@@ -71,14 +74,17 @@ class AudioDec(AudioCodec):
             rx = VocoderSession(self.decoder, batch, chunk // hop, graph)
         rx.load_state()
         rx.lookup_generator = self.rx_encoder
+        if codes:
+            tx.enable_codes()
+            rx.enable_codes()
         return tx, rx
 
-    def open_pool(self, capacity, chunk=300, graph=True):
+    def open_pool(self, capacity, chunk=300, graph=True, codes=False):
         """(tx_pool, rx_pool) for `capacity` independent streams, mirroring
         open_session: a ``StreamPool`` on the transmitter, a ``StreamPool`` or a
         ``VocoderPool`` (``chunk / hop`` frames per hop) on the receiver, both
         with the models' warmed-up pad_buffers as the template every newly
-        opened stream starts from."""
+        opened stream starts from.  ``codes=True`` as in ``open_session``."""
         from sel.streaming import StreamPool, VocoderPool
         if self.tx_encoder is None or self.rx_encoder is None or self.decoder is None:
             raise RuntimeError("open_pool: call load_transmitter and load_receiver first")
@@ -95,6 +101,9 @@ class AudioDec(AudioCodec):
             rx = VocoderPool(self.decoder, capacity, chunk // hop, graph)
         rx.load_state()
         rx.lookup_generator = self.rx_encoder
+        if codes:
+            tx.enable_codes()
+            rx.enable_codes()
         return tx, rx
 
 

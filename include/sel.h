@@ -374,6 +374,56 @@ int sel_rvq_bwd(const float* x, int64_t N, int D, const float* embed0, int K, co
                 const float* g_out, const float* g_loss, float commitment, float* g_x,
                 sel_stream_t stream);
 
+/* ---- residual VQ for a streaming hop: the quantizer and the lookup as step
+ * launches (csrc/vq_step.hip) --------------------------------------------------
+ * Both calls only enqueue one kernel: no allocation, no workspace, no host
+ * synchronisation, no prep launch, no state -- they can be captured in a graph
+ * behind / in front of the conv steps of a hop.  Arguments are validated before
+ * any device work (SEL_ERR_ARG).
+ *
+ * Active set (both): rows = B * rows_per_sample.  n_active NULL: every row is
+ * active.  Otherwise n_active is a DEVICE int32 and n = clamp(*n_active, 0, B);
+ * rows >= n * rows_per_sample are neither read nor written, and a block that
+ * lies entirely beyond them returns after reading the count (as the pool step
+ * kernels do).  There is no slot list: in and out are dense in active order.
+ *
+ * sel_rvq_step: z (rows, D) fp32 -> idx (S, rows) int64 and, unless zq is NULL,
+ * zq (rows, D) fp32.  embeds (S, D, K) fp32, the `embed` buffers stacked.  Per
+ * (row, stage, code) the arithmetic is sel_rvq_fwd's direct kernel exactly:
+ *   |r|^2: lanes over d (d = lane, lane + 64, ...), fmaf, then the wave's xor butterfly;
+ *   dot_k and |e_k|^2: fmaf chains over d ascending from 0, on the same loaded values;
+ *   dist_k = (|r|^2 - 2 dot_k) + |e_k|^2, idx = argmin, lowest index on ties;
+ *   q = e_idx, qst = r + (q - r), r <- r - qst, zq += qst (zq starts at 0).
+ * For finite z, idx (before the offset) and zq are bit for bit what sel_rvq_fwd
+ * writes under every setting of tune keys 2 and 39.  flatten != 0 adds s*K to
+ * stage s's picks (ResidualVQ.forward_index(flatten_idx=True): ids into the flat
+ * codebook).  The pick is forced into [0, K) before the gather: a row whose
+ * distances are all NaN picks code 0 and reads nothing outside the stack.
+ * One workgroup per row, threads over codes; a row's bits depend on that row
+ * alone.  D = 64 with K = 1024 takes a register-resident instance, everything
+ * else a generic loop with the same arithmetic.
+ * Accepted: rows >= 1, rows % rows_per_sample == 0, 0 < D <= 256, K > 0, S > 0
+ * (no upper limit on S: idx is written per stage); z, embeds, idx non-null; zq
+ * must not alias z.
+ *
+ * sel_rvq_lookup_step: idx (S, rows) int64, ids into codebook (ncodes, D) fp32
+ * (ResidualVQ.initial()'s flat layout, ncodes = S*K there) -> out (rows, D):
+ *   acc = codebook[idx[0,row]]; acc = acc + codebook[idx[s,row]] for s = 1 .. S-1
+ *   in that order, each a round-to-nearest fp32 add;
+ *   with mean / scale (D floats each, both or neither): acc = (acc - mean[d]) / scale[d],
+ *   a correctly rounded subtraction and division (HiFiGAN decode_norm);
+ *   stored as fp32, or as bf16 rounded to nearest even (out_dtype).
+ * An id outside [0, ncodes) contributes zero and nothing is read through it.
+ * 16-byte vectors where D % 4 == 0 and codebook / out / mean / scale are
+ * 16-byte aligned, element-wise otherwise (same bits).
+ * Accepted: rows >= 1, rows % rows_per_sample == 0, S > 0, D > 0, ncodes > 0;
+ * idx, codebook, out non-null. */
+int sel_rvq_step(const float* z, int rows, int rows_per_sample, int D, const float* embeds, int S, int K,
+                 const int32_t* n_active, int flatten, int64_t* idx, float* zq, sel_stream_t stream);
+int sel_rvq_lookup_step(const int64_t* idx, int rows, int rows_per_sample, int S, int64_t ncodes, int D,
+                        const float* codebook, const float* mean, const float* scale, const int32_t* n_active,
+                        int out_dtype, void* out, sel_stream_t stream);
+
 /* ---- residual VQ, training mode: the EMA codebook update, vq_module.py:74-80 ----
  * Runs after sel_rvq_fwd on the same x / embeds / idx / counts.  Training mode
  * changes nothing about the assignment (every stage picks its code with its own

@@ -44,6 +44,19 @@ into its parts, same protocol: the two graphs replayed alone, the same graphs
 captured without their commit / copy_slots launch, and the full calls (input
 fill + replay, and for the pool the staging of the slot list); writes
 profiles/stream_pool_attribution.{json,md} (the second table of DESIGN §15.3).
+
+  python tools/stream_bench.py --codes
+measures what the code indices inside the hop graphs save (enable_codes), same
+protocol, the paths alternating in one process on separate objects:
+
+  (a)  encode replay + quantize          against  (b)  transmit
+  (a') lookup + decode replay            against  (b') receive
+
+at B = 1 and B = --streams in a session and on a pool with all --streams slots
+active, chunk 300, with the AudioDec decoder and the v1 vocoder on the receiver,
+and writes profiles/stream_codes_bench.{json,md} (the table of DESIGN §16).
+Acceptance: at B = 1 the transmitter's (b) must be faster than (a) by more than
+the wider 5-95 % band; every other row must be no slower by the same band.
 """
 import argparse
 import json
@@ -363,6 +376,101 @@ def main_pool(a, dev):
     print("\n".join(lines + verdicts))
 
 
+def run_codes_config(kind, dtype, N, chunk, hops, warmup, dev):
+    """(a) / (b) of the transmitter and (a') / (b') of the receiver with the
+    AudioDec decoder and with the v1 vocoder, `kind` = "session" (batch N) or
+    "pool" (N of N slots active), at full width.  The old and the new path run
+    on separate objects fed the same input, so each advances its own state."""
+    from models.autoencoder.AudioDec import StreamGenerator as Encoder
+    from models.vocoder.HiFiGAN import StreamGenerator as Vocoder
+    from sel import configs
+    from sel.streaming import StreamPool, StreamSession, VocoderPool, VocoderSession
+    torch.manual_seed(93)
+    E = Encoder().to(dev).eval()
+    E.quantizer.initial()
+    V = Vocoder(**configs.VOCODER_V1).to(dev).eval()
+    L = chunk // 300
+    x = 0.1 * torch.randn(N, 1, chunk, generator=torch.Generator().manual_seed(1)).to(dev)
+    idx = E.quantize(E.encode(x))
+    pool = kind == "pool"
+    if pool:
+        idx = idx.view(idx.shape[0], N, L)
+
+    def make_ae():
+        return StreamPool(E, N, chunk, graph=True, dtype=dtype) if pool else StreamSession(E, N, chunk, graph=True,
+                                                                                           dtype=dtype)
+
+    def make_v1():
+        return VocoderPool(V, N, L, graph=True, dtype=dtype) if pool else VocoderSession(V, N, L, graph=True,
+                                                                                         dtype=dtype)
+
+    objs = {}
+    for name, make in (("ae", make_ae), ("v1", make_v1)):
+        old, new = make(), make()
+        for o in (old, new):
+            o.lookup_generator = E
+        new.enable_codes()
+        objs[name] = (old, new)
+    sl = ()
+    if pool:
+        for old, new in objs.values():
+            sl = ([old.open() for _ in range(N)],)
+            assert [new.open() for _ in range(N)] == sl[0]
+    ae_old, ae_new = objs["ae"]
+    v1_old, v1_new = objs["v1"]
+    paths = {"tx": (lambda: ae_old.quantize(ae_old.encode(*sl, x)), lambda: ae_new.transmit(*sl, x)),
+             "rx": (lambda: ae_old.decode(*sl, ae_old.lookup(idx)), lambda: ae_new.receive(*sl, idx)),
+             "rx_v1": (lambda: v1_old.decode(*sl, v1_old.lookup(idx)), lambda: v1_new.receive(*sl, idx))}
+    stream = torch.cuda.current_stream(dev)
+    rec = {h: {p: dict(host=[], gpu=[]) for p in ("old", "new")} for h in paths}
+    for hop in range(warmup + hops):
+        for half, fns in paths.items():
+            for p, fn in zip(("old", "new"), fns):
+                _, h, g = _timed(fn, stream)
+                if hop >= warmup:
+                    rec[half][p]["host"].append(h)
+                    rec[half][p]["gpu"].append(g)
+    return dict(kind=kind, dtype=str(dtype).replace("torch.", ""), streams=N, chunk=chunk, hops=hops,
+                halves={h: {p: {k: _stats(v) for k, v in r.items()} for p, r in d.items()} for h, d in rec.items()})
+
+
+def main_codes(a, dev):
+    results = []
+    for dt in a.dtypes:
+        for kind, N in (("session", 1), ("session", a.streams), ("pool", a.streams)):
+            r = run_codes_config(kind, getattr(torch, dt), N, 300, a.hops, a.warmup, dev)
+            results.append(r)
+            print(json.dumps(r), flush=True)
+    label = {("tx", "old"): "(a) encode replay + quantize", ("tx", "new"): "(b) transmit",
+             ("rx", "old"): "(a') lookup + decode replay", ("rx", "new"): "(b') receive",
+             ("rx_v1", "old"): "(a') lookup + v1 decode replay", ("rx_v1", "new"): "(b') v1 receive"}
+    lines = ["| dtype | object | half | path | host ms med (p5-p95) | GPU ms med (p5-p95) |", "|---|---|---|---|---|---|"]
+    verdicts = []
+    for r in results:
+        what = f"{r['kind']} B={r['streams']}" if r["kind"] == "session" else f"pool {r['streams']} of {r['streams']}"
+        for half, d in r["halves"].items():
+            for p in ("old", "new"):
+                h, g = d[p]["host"], d[p]["gpu"]
+                lines.append(f"| {r['dtype']} | {what} | {half} | {label[half, p]} | "
+                             f"{h['med']:.3f} ({h['p5']:.3f}-{h['p95']:.3f}) | "
+                             f"{g['med']:.3f} ({g['p5']:.3f}-{g['p95']:.3f}) |")
+            o, n = d["old"]["host"], d["new"]["host"]
+            gain = o["med"] - n["med"]
+            spread = max(o["p95"] - o["p5"], n["p95"] - n["p5"])
+            faster = half == "tx" and r["kind"] == "session" and r["streams"] == 1     # must win; the rest: no slower
+            met = gain > spread if faster else gain >= -spread
+            verdicts.append(f"acceptance {r['dtype']} {what} {half} ({'faster' if faster else 'no slower'}): old "
+                            f"{o['med']:.3f} ms - new {n['med']:.3f} ms = {gain:.3f} ms vs 5-95% band {spread:.3f} ms: "
+                            f"{'MET' if met else 'NOT MET'}")
+    out = a.out or os.path.join(REPO, "profiles", "stream_codes_bench")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out + ".json", "w") as f:
+        json.dump(results, f, indent=1)
+    with open(out + ".md", "w") as f:
+        f.write("\n".join(lines + [""] + verdicts) + "\n")
+    print("\n".join(lines + verdicts))
+
+
 def main_vocoder(a, dev):
     results = []
     for dec in a.decoder:
@@ -416,6 +524,9 @@ def main():
     ap.add_argument("--attribution", action="store_true",
                     help="with --pool: where the pool's time over the lockstep session goes "
                          "(profiles/stream_pool_attribution)")
+    ap.add_argument("--codes", action="store_true",
+                    help="quantize / lookup inside the hop graphs: encode + quantize against transmit, lookup + "
+                         "decode against receive (profiles/stream_codes_bench)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -423,6 +534,8 @@ def main():
     dev = torch.device("cuda:0")
     if a.attribution and not a.pool:
         sys.exit("stream_bench: --attribution goes with --pool")
+    if a.codes:
+        return main_codes(a, dev)
     if a.pool:
         return main_attribution(a, dev) if a.attribution else main_pool(a, dev)
     if a.decoder != ["audiodec"]:
