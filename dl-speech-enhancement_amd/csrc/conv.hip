@@ -15,6 +15,7 @@
 //   bf16:  v_mfma_f32_16x16x32_bf16 with fp32 accumulation (C3 path)
 // Weight gradients: split-M reduction with v_mfma_f32_16x16x4_f32 over
 // LDS-staged gout/input tiles, deterministic split reduce.
+// Weight packing, the replicate-pad fix-up and the cast live in conv_pack.hip.
 #include <algorithm>
 
 #include "conv_common.h"
@@ -2843,21 +2844,6 @@ constexpr int C1_TR = 256;    // rows per sample-aligned tile (weight gradient)
 constexpr int C1F_TR = 768;
 constexpr int C1_HALO = 64;   // max (K-1)*dil
 
-// Stage act(x) for input times [t0 - pad, t0 - pad + C1_TR + halo) of sample b as
-// fp32 in LDS, causal zero / replicate padding resolved here.
-__device__ __forceinline__ void c1_stage(const Args& a, const __bf16* __restrict__ in, int64_t b, int t0,
-                                         float* xs) {
-  const int span = C1_TR + (a.K - 1) * a.dil;
-  for (int r = threadIdx.x; r < span; r += 256) {
-    int ti = t0 - a.pad + r;
-    const bool inside = ti >= 0 && ti < a.T;
-    const bool ok = inside || a.pad_mode == SEL_PAD_REPLICATE;
-    ti = ti < 0 ? 0 : (ti >= a.T ? a.T - 1 : ti);
-    const float v = float(in[b * a.T + ti]);
-    xs[r] = ok ? (a.in_elu ? elu_fast(v) : v) : 0.f;
-  }
-}
-
 // Thread = (8-wide output group g, row lane rl): its 8 x K weights live in
 // registers; per row it reads K staged samples and writes one 16-B vector, the
 // NG lanes of a row together writing the row's contiguous N outputs.
@@ -4496,282 +4482,7 @@ __global__ __launch_bounds__(256) void k_split_sum2(const float* __restrict__ pa
   out[j] = acc;
 }
 
-// ---------------------------------------------------------------------------
-// weight packing
-// ---------------------------------------------------------------------------
-// strided fwd pack: Wp[co][tap][ph*Cin+ci] = W[co][ci][k(tap,ph)]
-__device__ __forceinline__ int strided_k(int tap, int ph, int s) {
-  if (tap == 0) return ph >= 1 ? ph - 1 : -1;
-  if (tap == 1) return ph + s - 1;
-  return ph == 0 ? 2 * s - 1 : -1;
-}
-
-template <typename TO>
-__global__ void k_pack(int kind, const float* __restrict__ w, int cout, int cin, int K, int s,
-                       TO* __restrict__ wp) {
-  int64_t total;
-  if (kind == SEL_PACK_FWD) total = int64_t(cout) * K * cin;
-  else if (kind == SEL_PACK_FWD_STRIDED) total = int64_t(cout) * 3 * s * cin;
-  else total = int64_t(s) * cout * 2 * cin;
-  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
-       i += int64_t(gridDim.x) * blockDim.x) {
-    float v = 0.f;
-    if (kind == SEL_PACK_FWD) {
-      const int c = int(i % cin);
-      const int k = int((i / cin) % K);
-      const int n = int(i / (int64_t(cin) * K));
-      v = w[(int64_t(n) * cin + c) * K + k];
-    } else if (kind == SEL_PACK_FWD_STRIDED) {
-      const int Cp = s * cin;
-      const int cp = int(i % Cp);
-      const int tap = int((i / Cp) % 3);
-      const int n = int(i / (int64_t(Cp) * 3));
-      const int ph = cp / cin, ci = cp % cin;
-      const int k = strided_k(tap, ph, s);
-      v = k >= 0 ? w[(int64_t(n) * cin + ci) * (2 * s) + k] : 0.f;
-    } else {  // CONVT: Wp[(ph*cout+co)][tap][ci] = Wt[ci][co][tap==0 ? ph+s : ph]
-      const int ci = int(i % cin);
-      const int tap = int((i / cin) % 2);
-      const int nn = int(i / (int64_t(cin) * 2));
-      const int ph = nn / cout, co = nn % cout;
-      const int k = tap == 0 ? ph + s : ph;
-      v = w[(int64_t(ci) * cout + co) * (2 * s) + k];
-    }
-    wp[i] = from_f<TO>(v);
-  }
-}
-
-template <typename T>
-__global__ void k_pack_dgrad(const T* __restrict__ wp, int N, int K, int C, T* __restrict__ wd) {
-  const int64_t total = int64_t(N) * K * C;
-  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
-       i += int64_t(gridDim.x) * blockDim.x) {
-    // wd[c][j][n] = wp[n][K-1-j][c]
-    const int n = int(i % N);
-    const int j = int((i / N) % K);
-    const int c = int(i / (int64_t(N) * K));
-    wd[i] = wp[(int64_t(n) * K + (K - 1 - j)) * C + c];
-  }
-}
-
-// Multi-tensor pack: every job's fwd pack Wp and (optionally) its dgrad form Wd
-// in ONE launch (the per-layer launches of sel_pack_weight + sel_pack_dgrad were
-// ~120 x 4 us per training step).  Grid-stride over TWO ranges of the
-// concatenated packed elements: [0, total) writes Wp in its own order, [total,
-// 2 total) writes Wd in ITS own order (gathering the source element), so both
-// write streams are coalesced (writing Wd as the transpose of the Wp walk made
-// every 2-B store its own partial line: 45 us per C3 step).  A thread
-// binary-searches its job in the device job table.
-template <typename TO>
-__global__ void k_pack_many(const sel_pack_job* __restrict__ jobs, int njobs, int64_t total) {
-  for (int64_t i2 = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i2 < 2 * total;
-       i2 += int64_t(gridDim.x) * blockDim.x) {
-    const bool dg = i2 >= total;  // dgrad-form range
-    const int64_t i = dg ? i2 - total : i2;
-    int lo = 0, hi = njobs - 1;
-    while (lo < hi) {
-      const int mid = (lo + hi + 1) >> 1;
-      if (jobs[mid].offset <= i) lo = mid;
-      else hi = mid - 1;
-    }
-    const sel_pack_job& J = jobs[lo];
-    if (dg && !J.wdgrad) continue;
-    // a layer's packed index fits 32 bits (host-checked): unsigned 32-bit
-    // division instead of the 64-bit sequences (the per-step pack of the C3
-    // weights took 105 us with them)
-    const unsigned li = unsigned(i - J.offset);
-    const unsigned s = unsigned(J.stride), cin = unsigned(J.cin), cout = unsigned(J.cout), K = unsigned(J.k);
-    // packed geometry: Wp[n][kp][cp] (N rows, KP taps, CP channels per tap)
-    unsigned N, KP, CP;
-    if (J.kind == SEL_PACK_FWD) N = cout, KP = K, CP = cin;
-    else if (J.kind == SEL_PACK_FWD_STRIDED) N = cout, KP = 3, CP = s * cin;
-    else N = s * cout, KP = 2, CP = cin;
-    unsigned n, kp, cp;
-    if (!dg) {  // li = (n * KP + kp) * CP + cp
-      const unsigned q = li / CP;
-      cp = li - q * CP;
-      n = q / KP;
-      kp = q - n * KP;
-    } else {  // Wd[c][j][n] = Wp[n][KP-1-j][c]: li = (cp * KP + j) * N + n
-      const unsigned r = li / N;
-      n = li - r * N;
-      cp = r / KP;
-      kp = KP - 1 - (r - cp * KP);
-    }
-    float v = 0.f;
-    if (J.kind == SEL_PACK_FWD) {
-      v = J.w[(n * cin + cp) * K + kp];
-    } else if (J.kind == SEL_PACK_FWD_STRIDED) {
-      const unsigned ph = cp / cin, ci = cp - ph * cin;
-      const int k = strided_k(int(kp), int(ph), int(s));
-      v = k >= 0 ? J.w[(n * cin + ci) * (2 * s) + unsigned(k)] : 0.f;
-    } else {
-      const unsigned ph = n / cout, co = n - ph * cout;
-      const unsigned k = kp == 0 ? ph + s : ph;
-      v = J.w[(cp * cout + co) * (2 * s) + k];
-    }
-    static_cast<TO*>(dg ? J.wdgrad : J.wpack)[li] = from_f<TO>(v);
-  }
-}
-
-// The same with the job table in the kernel arguments (sel_pack_many_host): no
-// device copy of the table, hence no pinned staging and no host-to-device copy
-// in the step (the pinned allocation + copy per weight update of the device-table
-// form left the GPU idle ~0.3 ms per C3 step while the host waited on them).
-// A launch packs the element range [lo, hi) of `total` that its jobs cover.
-constexpr int PM_MAXJ = 48;
-struct PackJobs {
-  sel_pack_job j[PM_MAXJ];
-  int n;
-};
-template <typename TO>
-__global__ void k_pack_many_arg(PackJobs pj, int64_t lo, int64_t hi, int64_t total) {
-  const int64_t len = hi - lo;
-  for (int64_t i2 = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i2 < 2 * len;
-       i2 += int64_t(gridDim.x) * blockDim.x) {
-    const bool dg = i2 >= len;
-    const int64_t i = lo + (dg ? i2 - len : i2);
-    int a = 0, b = pj.n - 1;
-    while (a < b) {
-      const int mid = (a + b + 1) >> 1;
-      if (pj.j[mid].offset <= i) a = mid;
-      else b = mid - 1;
-    }
-    const sel_pack_job& J = pj.j[a];
-    if (dg && !J.wdgrad) continue;
-    const unsigned li = unsigned(i - J.offset);
-    const unsigned s = unsigned(J.stride), cin = unsigned(J.cin), cout = unsigned(J.cout), K = unsigned(J.k);
-    unsigned N, KP, CP;
-    if (J.kind == SEL_PACK_FWD) N = cout, KP = K, CP = cin;
-    else if (J.kind == SEL_PACK_FWD_STRIDED) N = cout, KP = 3, CP = s * cin;
-    else N = s * cout, KP = 2, CP = cin;
-    unsigned n, kp, cp;
-    if (!dg) {
-      const unsigned q = li / CP;
-      cp = li - q * CP;
-      n = q / KP;
-      kp = q - n * KP;
-    } else {
-      const unsigned r = li / N;
-      n = li - r * N;
-      cp = r / KP;
-      kp = KP - 1 - (r - cp * KP);
-    }
-    float v = 0.f;
-    if (J.kind == SEL_PACK_FWD) {
-      v = J.w[(n * cin + cp) * K + kp];
-    } else if (J.kind == SEL_PACK_FWD_STRIDED) {
-      const unsigned ph = cp / cin, ci = cp - ph * cin;
-      const int k = strided_k(int(kp), int(ph), int(s));
-      v = k >= 0 ? J.w[(n * cin + ci) * (2 * s) + unsigned(k)] : 0.f;
-    } else {
-      const unsigned ph = n / cout, co = n - ph * cout;
-      const unsigned k = kp == 0 ? ph + s : ph;
-      v = J.w[(cp * cout + co) * (2 * s) + k];
-    }
-    static_cast<TO*>(dg ? J.wdgrad : J.wpack)[li] = from_f<TO>(v);
-  }
-  (void)total;
-}
-
-// Tiled form of k_pack_many_arg (the product's per-step repack): a workgroup
-// owns a 32 (n) x 32 (cp) x KP tile of one job's packed geometry, gathers it
-// from the torch-layout weight with (cp, kp)-contiguous reads into an fp32 LDS
-// tile, then writes the tile's forward form Wp[n][kp][cp] (32 consecutive cp per
-// run) and its dgrad form Wd[cp][KP-1-kp][n] (32 consecutive n per run): both
-// forms leave as coalesced runs.  The per-element form gathered the dgrad
-// form's source across whole weight rows (one cache line per lane): 72 us per
-// C3 step for 31 MB of traffic (rocprof, profiles/r6f_kernel_stats.md).  Same
-// values (a copy with the same rounding).
-constexpr int PT_T = 32, PT_KMAX = 8, PT_P = PT_T + 1;
-struct PackTiles {
-  sel_pack_job j[PM_MAXJ];
-  int tstart[PM_MAXJ + 1];  // first tile of each job; tstart[n] = tile count
-  int n;
-};
-__device__ __forceinline__ void pack_geom(const sel_pack_job& J, unsigned& N, unsigned& KP, unsigned& CP) {
-  const unsigned s = unsigned(J.stride), cin = unsigned(J.cin), cout = unsigned(J.cout), K = unsigned(J.k);
-  if (J.kind == SEL_PACK_FWD) N = cout, KP = K, CP = cin;
-  else if (J.kind == SEL_PACK_FWD_STRIDED) N = cout, KP = 3, CP = s * cin;
-  else N = s * cout, KP = 2, CP = cin;
-}
-// 1024 threads: one (n, cp) pair of the 32 x 32 tile per thread, with all its
-// KP taps, so no index needs a division by the job's tap count, and the KP
-// loads of a pair are all issued before its LDS stores.  (At 256 threads, four
-// elements a thread one after another, the small launches of a C3 step -- 32-64
-// tiles, one workgroup each -- took 17-18 us; now 6-7 us, and the 640-tile
-// launch 11.4 -> 9.8 us.)
-template <typename TO, unsigned PT_THREADS>
-__global__ __launch_bounds__(PT_THREADS) void k_pack_tiles(PackTiles pt) {
-  __shared__ float tile[PT_T * PT_KMAX * PT_P];
-  int a = 0, b = pt.n - 1;
-  const int t = int(blockIdx.x);
-  while (a < b) {  // block-uniform
-    const int mid = (a + b + 1) >> 1;
-    if (pt.tstart[mid] <= t) a = mid;
-    else b = mid - 1;
-  }
-  const sel_pack_job& J = pt.j[a];
-  unsigned N, KP, CP;
-  pack_geom(J, N, KP, CP);
-  const unsigned s = unsigned(J.stride), cin = unsigned(J.cin), cout = unsigned(J.cout), K = unsigned(J.k);
-  const unsigned ntc = (CP + PT_T - 1) / PT_T;
-  const unsigned lt = unsigned(t - pt.tstart[a]);
-  const unsigned n0 = (lt / ntc) * PT_T, c0 = (lt % ntc) * PT_T;
-  // gather: pair (nl, cl), cl fastest; its KP taps are contiguous in the FWD
-  // source; out-of-range taps load w[0] and are replaced by zeros
-  for (unsigned r = threadIdx.x; r < PT_T * PT_T; r += PT_THREADS) {
-    const unsigned cl = r % PT_T, nl = r / PT_T;
-    const unsigned n = n0 + nl, cp = c0 + cl;
-    const bool in = n < N && cp < CP;
-    unsigned base = 0, ph = 0;
-    if (J.kind == SEL_PACK_FWD) {
-      base = (n * cin + cp) * K;
-    } else if (J.kind == SEL_PACK_FWD_STRIDED) {
-      ph = cp / cin;
-      base = (n * cin + (cp - ph * cin)) * (2 * s);
-    } else {
-      ph = n / cout;
-      base = (cp * cout + (n - ph * cout)) * (2 * s);
-    }
-    float v[PT_KMAX];
-    bool ok[PT_KMAX];
-#pragma unroll
-    for (unsigned kp = 0; kp < PT_KMAX; ++kp) {
-      if (kp >= KP) break;  // block-uniform
-      int k = int(kp);
-      if (J.kind == SEL_PACK_FWD_STRIDED) k = strided_k(int(kp), int(ph), int(s));
-      else if (J.kind == SEL_PACK_CONVT) k = int(kp == 0 ? ph + s : ph);
-      ok[kp] = in && k >= 0;
-      v[kp] = J.w[ok[kp] ? base + unsigned(k) : 0];
-    }
-#pragma unroll
-    for (unsigned kp = 0; kp < PT_KMAX; ++kp) {
-      if (kp >= KP) break;
-      tile[(nl * KP + kp) * PT_P + cl] = ok[kp] ? v[kp] : 0.f;
-    }
-  }
-  __syncthreads();
-  TO* const wp = static_cast<TO*>(J.wpack);
-  for (unsigned r = threadIdx.x; r < PT_T * PT_T; r += PT_THREADS) {  // Wp[n][kp][cp]: cp fastest
-    const unsigned cl = r % PT_T, nl = r / PT_T;
-    const unsigned n = n0 + nl, cp = c0 + cl;
-    if (n < N && cp < CP)
-      for (unsigned kp = 0; kp < KP; ++kp) wp[(n * KP + kp) * CP + cp] = from_f<TO>(tile[(nl * KP + kp) * PT_P + cl]);
-  }
-  if (J.wdgrad) {
-    TO* const wd = static_cast<TO*>(J.wdgrad);
-    for (unsigned r = threadIdx.x; r < PT_T * PT_T; r += PT_THREADS) {  // Wd[cp][j][n]: n fastest
-      const unsigned nl = r % PT_T, cl = r / PT_T;
-      const unsigned n = n0 + nl, cp = c0 + cl;
-      if (n < N && cp < CP)
-        for (unsigned j = 0; j < KP; ++j)
-          wd[(cp * KP + j) * N + n] = from_f<TO>(tile[(nl * KP + (KP - 1 - j)) * PT_P + cl]);
-    }
-  }
-}
-
-// Packed index of torch-layout weight element i (the gather map of k_unpack).
+// Packed index of torch-layout weight element i (the gather map of k_unpack, conv_pack.hip).
 __device__ __forceinline__ int64_t unpack_src(int kind, int64_t i, int cout, int cin, int K, int s) {
   if (kind == SEL_PACK_FWD) {
     const int k = int(i % K);
@@ -4838,83 +4549,6 @@ __global__ __launch_bounds__(256) void k_split_finish1(const float* __restrict__
   }
 }
 
-__global__ void k_unpack(int kind, const float* __restrict__ gp, int cout, int cin, int K, int s,
-                         float* __restrict__ gw) {
-  // iterate over torch-layout elements
-  int64_t total = (kind == SEL_PACK_CONVT) ? int64_t(cin) * cout * 2 * s
-                                           : int64_t(cout) * cin * (kind == SEL_PACK_FWD ? K : 2 * s);
-  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < total;
-       i += int64_t(gridDim.x) * blockDim.x) {
-    float v;
-    if (kind == SEL_PACK_FWD) {
-      const int k = int(i % K);
-      const int ci = int((i / K) % cin);
-      const int co = int(i / (int64_t(K) * cin));
-      v = gp[(int64_t(co) * K + k) * cin + ci];
-    } else if (kind == SEL_PACK_FWD_STRIDED) {
-      const int KK = 2 * s;
-      const int k = int(i % KK);
-      const int ci = int((i / KK) % cin);
-      const int co = int(i / (int64_t(KK) * cin));
-      int tap, ph;
-      if (k <= s - 2) { tap = 0; ph = k + 1; }
-      else if (k <= 2 * s - 2) { tap = 1; ph = k - s + 1; }
-      else { tap = 2; ph = 0; }
-      v = gp[(int64_t(co) * 3 + tap) * (int64_t(s) * cin) + ph * cin + ci];
-    } else {
-      const int KK = 2 * s;
-      const int k = int(i % KK);
-      const int co = int((i / KK) % cout);
-      const int ci = int(i / (int64_t(KK) * cout));
-      const int ph = k < s ? k : k - s;
-      const int tap = k < s ? 1 : 0;
-      v = gp[(int64_t(ph * cout + co) * 2 + tap) * cin + ci];
-    }
-    gw[i] = v;
-  }
-}
-
-// adjoint of the replicate pad: gin[b*T, c] += sum_n gout[b*T, n] * Wp[n][0][c]
-// block = (sample b, 64 channels); 16 waves split n, LDS reduce.
-template <typename T>
-__global__ __launch_bounds__(1024) void k_replicate_fix(Args a, const T* __restrict__ gout, const T* __restrict__ wp,
-                                                        T* __restrict__ gin) {
-  __shared__ float red[16][64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t row = int64_t(blockIdx.x) * a.T;
-  const int c = blockIdx.y * 64 + lane;
-  float s = 0.f;
-  if (c < a.C) {
-    // 8 (gout, weight) pairs in flight per step, summed in the same n order
-    int n = wave;
-    for (; n + 16 * 7 < a.N; n += 16 * 8) {
-      float gv[8], wv[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        gv[u] = to_f(gout[row * a.N + n + 16 * u]);
-        wv[u] = to_f(wp[(int64_t(n + 16 * u) * a.K + 0) * a.C + c]);
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s += gv[u] * wv[u];
-    }
-    for (; n < a.N; n += 16) s += to_f(gout[row * a.N + n]) * to_f(wp[(int64_t(n) * a.K + 0) * a.C + c]);
-  }
-  red[wave][lane] = s;
-  __syncthreads();
-  if (wave == 0 && c < a.C) {
-    float t = 0.f;
-    for (int w = 0; w < 16; ++w) t += red[w][lane];
-    gin[row * a.C + c] = from_f<T>(to_f(gin[row * a.C + c]) + t);
-  }
-}
-
-template <typename TS, typename TD>
-__global__ void k_cast(const TS* __restrict__ s, TD* __restrict__ d, int64_t n) {
-  for (int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
-       i += int64_t(gridDim.x) * blockDim.x)
-    d[i] = from_f<TD>(to_f(s[i]));
-}
-
 }  // namespace conv
 }  // namespace sel
 
@@ -4924,7 +4558,8 @@ __global__ void k_cast(const TS* __restrict__ s, TD* __restrict__ d, int64_t n) 
 using namespace sel;
 using namespace sel::conv;
 
-namespace {
+namespace sel {
+namespace conv {
 
 int check_desc(const sel_conv_desc* d) {
   SEL_REQUIRE(d != nullptr, SEL_ERR_ARG, "null conv descriptor");
@@ -4961,6 +4596,11 @@ Args to_args(const sel_conv_desc* d) {
   return a;
 }
 
+}  // namespace conv
+}  // namespace sel
+
+namespace {
+
 template <typename TI, typename TO, int BM, int BN>
 size_t fwd_lds(const Args& a) {
   const size_t stage = (size_t(BM + (a.K - 1) * a.dil) + size_t(a.K) * BN) * Pitch<TI>::v * sizeof(TI);
@@ -4994,20 +4634,11 @@ int launch_fwd_f32(const Args& a, const void* in, const void* wp, const float* b
   const int64_t tiles = (a.rows / a.T) * ((a.T + BM - 1) / BM);  // sample-aligned tiles
   if (tiles == 0) return SEL_OK;
   dim3 grid(unsigned(tiles), unsigned(a.N / BN));
-  const void* kern = a.K == 1 ? (const void*)k_conv_fwd_f32<1, BM, BN>
-                     : a.K <= 3 ? (const void*)k_conv_fwd_f32<3, BM, BN> : (const void*)k_conv_fwd_f32<8, BM, BN>;
-  if (lds > 64 * 1024) SEL_HIP(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
-  const float* x = static_cast<const float*>(in);
-  const float* w = static_cast<const float*>(wp);
-  const float* ax = static_cast<const float*>(aux);
-  const float* rs = static_cast<const float*>(res);
-  float* o = static_cast<float*>(out);
-  if (a.K == 1)
-    hipLaunchKernelGGL((k_conv_fwd_f32<1, BM, BN>), grid, dim3(256), lds, s, a, x, w, bias, ax, rs, o);
-  else if (a.K <= 3)
-    hipLaunchKernelGGL((k_conv_fwd_f32<3, BM, BN>), grid, dim3(256), lds, s, a, x, w, bias, ax, rs, o);
-  else
-    hipLaunchKernelGGL((k_conv_fwd_f32<8, BM, BN>), grid, dim3(256), lds, s, a, x, w, bias, ax, rs, o);
+  auto kern = a.K == 1 ? k_conv_fwd_f32<1, BM, BN> : a.K <= 3 ? k_conv_fwd_f32<3, BM, BN> : k_conv_fwd_f32<8, BM, BN>;
+  if (lds > 64 * 1024)
+    SEL_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds)));
+  hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, a, static_cast<const float*>(in), static_cast<const float*>(wp),
+                     bias, static_cast<const float*>(aux), static_cast<const float*>(res), static_cast<float*>(out));
   SEL_LAUNCH_CHECK();
   return SEL_OK;
 }
@@ -5112,8 +4743,6 @@ int launch_ws_k(const Args& a, const void* in, const void* wp, const float* bias
 }
 
 
-// Variant the dispatcher picks for a bf16 forward launch (see fwd4_variant);
-// -1 when the generic (non-pipelined) kernel is used.
 // the sample-tile kernel (conv_wss.hip, variant 30) for the 256-wide layers at
 // T = 400: tune key 47 = 1 on, 2 off, 0 = kWssDefault
 constexpr bool kWssDefault = true;
@@ -5149,8 +4778,6 @@ bool wss_pick_elu(const Args& a) {
          a.pad_mode == SEL_PAD_ZERO && wss_ok(a) && wss_geometry(a, S, tm) && S == 16;
 }
 
-// out_f32: an fp32-output launch (the sample-tile kernel takes those at T <= 400
-// only, wss_ok_out; fwd4_variant's dispatch applies the same condition)
 // the sample-tile kernel on five-sample tiles for the T = 80 layers (the C3
 // down / up convs at the 512-wide stage and their adjoints run on 128 x 32 tiles
 // at 80 of 128 rows per tile).  Measured in round 6: 55.7 -> 52.7, 50.6 -> 45.4,
@@ -5164,27 +4791,46 @@ bool wss_pick_short(const Args& a) {
   return (k == 1 || (k == 3 && a.N >= 512)) && wss_spt(a) > 1 && a.N % 64 == 0 && wss_ok(a);
 }
 
+// Variant of a bf16 forward launch on the pipelined kernels (fwd4_variant
+// launches it), -1 when the generic (non-pipelined) kernel is used.  Tune key
+// 0 = 21-30 forces a variant where its shape is legal.  out_f32: an fp32-output
+// launch (the sample-tile kernel takes those at T <= 400 only, wss_ok_out).
 int fwd4_choice(const Args& a, bool out_f32) {
   const int v = tune(0);
   if (!((a.C % CK) == 0 && (a.K - 1) * a.dil <= F4_HALOMAX && a.K <= 8 && (v == 0 || v > 20))) return -1;
-  if (v > 20 && (v != 27 || ws_ok(a)) && (v != 28 || ws8_gen_ok(a)) && (v != 29 || ws8w_ok(a)) &&
+  if (v > 20 && v <= 30 && (v != 27 || ws_ok(a)) && (v != 28 || ws8_gen_ok(a)) && (v != 29 || ws8w_ok(a)) &&
       (v != 30 || wss_ok_out(a, out_f32)))
     return v;
+  // heuristic from tools/conv_bench.py on the C3 layer shapes (profiles/r1_conv_bench.md):
+  // narrow / non-64-multiple outputs and short row counts favour 128x32 tiles
+  // (more workgroups in flight); wide layers 128x64 or 256x64.
   // (the T = 80 layers: 128 x 64 / 128 x 128 / 64 x 128 tiles measured 13-50 us
   // slower per graph-replayed C3 step, round 6)
   if (wss_pick_short(a) && wss_ok_out(a, out_f32)) return 30;
   if (a.N <= 32 || (a.N % 64) != 0 || a.rows < 8192) return 22;
+  // 256-wide 1x1 (RU256 1x1 fwd 27.5 -> 20.9 us, dgrad 22.5 -> 19.2): 64x128 tiles
   if (a.N >= 256 && a.K == 1) return 26;
+  // 256-wide layers at 400 samples x 64 clips (25.6k rows): the warp-specialised
+  // 256x128 kernel where legal (rocprofv3 kernel trace, profiles/r2_ws_conv.md:
+  // RU256 k7 fwd+dgrad 43.5 -> 38.4 us, down2 46.6 -> 41.8), else 256x64 tiles
+  // (RU256 k7 fwd 50.7 -> 36.2 us, dgrad 54.2 -> 43.0, down2 51.2 -> 43.1)
   if (a.N >= 256 && a.rows >= 16384)
     return wss_pick(a) && wss_ok_out(a, out_f32) ? 30 : tune(38) == 1 && ws8w_ok(a) ? 29 : ws_ok(a) ? 27 : 24;
   if (a.N <= 64 || a.rows < 65536) return 23;
+  // 128-wide layers at >= 64 k rows on the warp-specialised kernel (one
+  // 128-column tile: no input re-read across column tiles) for the k7 dgrads
+  // (RU128 d9: 63.6 -> 53.2 us) and the k3 convs (down1: 49.3 -> 44.1 us), not
+  // the k7 forwards with their ELU'd 54-row halo (48.6 -> 52.9 us);
+  // tools/conv_bench.py.
   if ((wss_pick_tall(a) || wss_pick_elu(a)) && wss_ok_out(a, out_f32)) return 30;
   if (ws8_gen_pick(a)) return 28;
   if (a.N == 128 && ws_ok(a) && (a.K <= 3 || (a.K == 7 && a.pad == 0 && !a.in_elu))) return 27;
+  // 128-wide k7 dgrad at 2000 samples (pad 0, no input ELU): 128x32 tiles (76.5 -> 62.6 us)
   if (a.N == 128 && a.K > 1 && a.pad == 0 && !a.in_elu) return 22;
   return 24;
 }
 
+// launches variant v = fwd4_choice(a, TO is fp32)
 template <int KMAX, typename TO>
 int fwd4_variant(int v, const Args& a, const void* in, const void* wp, const float* bias, const void* aux,
                  const void* res, void* out, hipStream_t s) {
@@ -5194,61 +4840,18 @@ int fwd4_variant(int v, const Args& a, const void* in, const void* wp, const flo
     case 23: return launch_fwd4<128, 64, 2, KMAX, TO>(a, in, wp, bias, aux, res, out, s);
     case 24: return launch_fwd4<256, 64, 4, KMAX, TO>(a, in, wp, bias, aux, res, out, s);
     case 25: return launch_fwd4<128, 128, 2, KMAX, TO>(a, in, wp, bias, aux, res, out, s);
-    case 26: return launch_fwd4<64, 128, 1, KMAX, TO>(a, in, wp, bias, aux, res, out, s);
-    case 27:
-      if (!ws_ok(a)) break;
-      return launch_ws_k<TO>(a, in, wp, bias, aux, res, out, s);
-    case 28:
-      if (!ws8_gen_ok(a)) break;
-      return launch_ws8<7, TO, 512, 128, 64>(a, in, wp, bias, aux, res, out, s);
+    case 27: return launch_ws_k<TO>(a, in, wp, bias, aux, res, out, s);
+    case 28: return launch_ws8<7, TO, 512, 128, 64>(a, in, wp, bias, aux, res, out, s);
     case 29:
-      if (!ws8w_ok(a)) break;
       if (a.K == 7) return launch_ws8<7, TO, 256, 128, 64, 2>(a, in, wp, bias, aux, res, out, s);
       return launch_ws8<3, TO, 256, 128, 64, 2>(a, in, wp, bias, aux, res, out, s);
-    case 30:
-      if (!wss_ok_out(a, sizeof(TO) == 4)) break;
-      return launch_wss<TO>(a, in, wp, bias, aux, res, out, s);
-    default: break;
+    case 30: return launch_wss<TO>(a, in, wp, bias, aux, res, out, s);
+    default: return launch_fwd4<64, 128, 1, KMAX, TO>(a, in, wp, bias, aux, res, out, s);  // 26
   }
-  // heuristic from tools/conv_bench.py on the C3 layer shapes (profiles/r1_conv_bench.md):
-  // narrow / non-64-multiple outputs and short row counts favour 128x32 tiles
-  // (more workgroups in flight); wide layers 128x64 or 256x64.
-  if (wss_pick_short(a) && wss_ok_out(a, sizeof(TO) == 4)) return launch_wss<TO>(a, in, wp, bias, aux, res, out, s);
-  if (a.N <= 32 || (a.N % 64) != 0 || a.rows < 8192)
-    return launch_fwd4<128, 32, 4, KMAX, TO>(a, in, wp, bias, aux, res, out, s);
-  // 256-wide 1x1 (RU256 1x1 fwd 27.5 -> 20.9 us, dgrad 22.5 -> 19.2): 64x128 tiles
-  if (a.N >= 256 && a.K == 1) return launch_fwd4<64, 128, 1, KMAX, TO>(a, in, wp, bias, aux, res, out, s);
-  // 256-wide layers at 400 samples x 64 clips (25.6k rows): the warp-specialised
-  // 256x128 kernel where legal (rocprofv3 kernel trace, profiles/r2_ws_conv.md:
-  // RU256 k7 fwd+dgrad 43.5 -> 38.4 us, down2 46.6 -> 41.8), else 256x64 tiles
-  // (RU256 k7 fwd 50.7 -> 36.2 us, dgrad 54.2 -> 43.0, down2 51.2 -> 43.1)
-  if (a.N >= 256 && a.rows >= 16384) {
-    if (wss_pick(a) && wss_ok_out(a, sizeof(TO) == 4)) return launch_wss<TO>(a, in, wp, bias, aux, res, out, s);
-    if (tune(38) == 1 && ws8w_ok(a)) return fwd4_variant<KMAX, TO>(29, a, in, wp, bias, aux, res, out, s);
-    if (ws_ok(a)) return launch_ws_k<TO>(a, in, wp, bias, aux, res, out, s);
-    return launch_fwd4<256, 64, 4, KMAX, TO>(a, in, wp, bias, aux, res, out, s);
-  }
-  if (a.N <= 64 || a.rows < 65536) return launch_fwd4<128, 64, 2, KMAX, TO>(a, in, wp, bias, aux, res, out, s);
-  // 128-wide layers at >= 64 k rows on the warp-specialised kernel (one
-  // 128-column tile: no input re-read across column tiles) for the k7 dgrads
-  // (RU128 d9: 63.6 -> 53.2 us) and the k3 convs (down1: 49.3 -> 44.1 us), not
-  // the k7 forwards with their ELU'd 54-row halo (48.6 -> 52.9 us);
-  // tools/conv_bench.py.
-  if ((wss_pick_tall(a) || wss_pick_elu(a)) && wss_ok_out(a, sizeof(TO) == 4))
-    return launch_wss<TO>(a, in, wp, bias, aux, res, out, s);
-  if (ws8_gen_pick(a)) return launch_ws8<7, TO, 512, 128, 64>(a, in, wp, bias, aux, res, out, s);
-  if (a.N == 128 && ws_ok(a) && (a.K <= 3 || (a.K == 7 && a.pad == 0 && !a.in_elu)))
-    return launch_ws_k<TO>(a, in, wp, bias, aux, res, out, s);
-  // 128-wide k7 dgrad at 2000 samples (pad 0, no input ELU): 128x32 tiles (76.5 -> 62.6 us)
-  if (a.N == 128 && a.K > 1 && a.pad == 0 && !a.in_elu)
-    return launch_fwd4<128, 32, 4, KMAX, TO>(a, in, wp, bias, aux, res, out, s);
-  return launch_fwd4<256, 64, 4, KMAX, TO>(a, in, wp, bias, aux, res, out, s);
 }
 
 // Weight-stationary thin kernel (tune key 4: 0 = use where legal, 1 = off;
-// key 5: target workgroup count, 0 = 1024).  Returns kNotThin when the shape
-// has no instance.
-constexpr int kNotThin = 1;
+// key 5: target workgroup count, 0 = 1024).
 
 template <int C, int N, int K, int R, bool E>
 int launch_thin(const Args& a, const void* in, const void* wp, const float* bias, const void* aux,
@@ -5259,18 +4862,11 @@ int launch_thin(const Args& a, const void* in, const void* wp, const float* bias
   // one round of resident workgroups (each pays the weight-fragment prologue
   // once; a grid just past the resident capacity would add a whole round for
   // its tail); tune key 5 > 0 overrides the workgroup target
-  static const int64_t slots = [] {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_conv_thin_bf16<C, N, K, R, E>, 256, G::LDS_TOTAL) !=
-            hipSuccess)
-      return int64_t(0);
-    return int64_t(cus) * per_cu / 8 * 8;
-  }();
+  static const int64_t slots =
+      resident_blocks((const void*)k_conv_thin_bf16<C, N, K, R, E>, 256, G::LDS_TOTAL) / 8 * 8;
   const int64_t target = tune(5) > 0 ? tune(5) : (slots > 0 ? slots : 1024);
-  const int64_t tpb = std::max<int64_t>(1, (ntiles + target - 1) / target);
-  const unsigned nb = unsigned(((ntiles + tpb - 1) / tpb + 7) / 8 * 8);  // multiple of 8 (XCD map)
+  const int64_t tpb = tiles_per_block(ntiles, target);
+  const unsigned nb = unsigned(blocks_for8(ntiles, tpb));  // multiple of 8 (XCD map)
   hipLaunchKernelGGL((k_conv_thin_bf16<C, N, K, R, E>), dim3(nb), dim3(256), G::LDS_TOTAL, s, a,
                      static_cast<const __bf16*>(in), static_cast<const __bf16*>(wp), bias,
                      static_cast<const __bf16*>(aux), static_cast<const __bf16*>(res), static_cast<__bf16*>(out),
@@ -5302,16 +4898,6 @@ int thin_index(const Args& a) {
   return -1;
 }
 
-bool thin_ok(const Args& a) { return thin_index(a) >= 0; }
-
-int thin_rows(const Args& a) {
-  const int i = thin_index(a);
-#define SEL_THIN_R(I_, C_, N_, K_, R_, R2_) if (i == I_) return (tune(6) >> I_) & 1 ? R2_ : R_;
-  SEL_THIN_SHAPES(SEL_THIN_R)
-#undef SEL_THIN_R
-  return 0;
-}
-
 // measured per layer (tools/conv_bench.py 30 34 35 36 37, profiles/r1_conv_bench_epf.md):
 // the prefetch pays on the k7 dgrads (ELU'(aux) operand) at 32 channels /
 // 256 rows (113 -> 88 us) and 64 channels / 64 rows (77 -> 72 us); on the
@@ -5334,22 +4920,19 @@ bool thin_variant(const Args& a, bool has_epilogue, int& rows) {
   return epf;
 }
 
-int dispatch_thin(const Args& a, const void* in, const void* wp, const float* bias, const void* aux,
-                  const void* res, void* out, hipStream_t s) {
-  const int i = thin_index(a);
-  if (i < 0) return kNotThin;
-  int rows_unused;
-  const bool epf = thin_variant(a, aux || res, rows_unused);
-  const bool alt = (((tune(6) >> i) & 1) != 0) != (epf && ((kThinEpfAlt >> i) & 1));
-#define SEL_THIN_LAUNCH(I_, C_, N_, K_, R_, R2_)                                             \
-  if (i == I_)                                                                               \
-    return epf ? (alt ? launch_thin<C_, N_, K_, R2_, true>(a, in, wp, bias, aux, res, out, s)   \
-                      : launch_thin<C_, N_, K_, R_, true>(a, in, wp, bias, aux, res, out, s))   \
-               : (alt ? launch_thin<C_, N_, K_, R2_, false>(a, in, wp, bias, aux, res, out, s)  \
-                      : launch_thin<C_, N_, K_, R_, false>(a, in, wp, bias, aux, res, out, s));
+// instance i (thin_index) with the E flag and tile rows of thin_variant
+int launch_thin_variant(int i, bool e, int rows, const Args& a, const void* in, const void* wp, const float* bias,
+                        const void* aux, const void* res, void* out, hipStream_t s) {
+#define SEL_THIN_LAUNCH(I_, C_, N_, K_, R_, R2_)                                                   \
+  if (i == I_)                                                                                     \
+    return e ? (rows == R2_ ? launch_thin<C_, N_, K_, R2_, true>(a, in, wp, bias, aux, res, out, s)   \
+                            : launch_thin<C_, N_, K_, R_, true>(a, in, wp, bias, aux, res, out, s))   \
+             : (rows == R2_ ? launch_thin<C_, N_, K_, R2_, false>(a, in, wp, bias, aux, res, out, s)  \
+                            : launch_thin<C_, N_, K_, R_, false>(a, in, wp, bias, aux, res, out, s));
   SEL_THIN_SHAPES(SEL_THIN_LAUNCH)
 #undef SEL_THIN_LAUNCH
-  return kNotThin;
+  set_error("no thin kernel instance %d", i);
+  return SEL_ERR_STATE;
 }
 
 // Fused residual-unit forward instances: (C, K, R) = (32, 7, 128), (64, 7, 64).
@@ -5360,8 +4943,8 @@ int launch_ru_thin(const Args& a, const void* in, const void* w1p, const float* 
   const int64_t ntiles = (a.rows / a.T) * ((a.T + R - 1) / R);
   if (ntiles == 0) return SEL_OK;
   const int64_t target = 1024;
-  const int64_t tpb = std::max<int64_t>(1, (ntiles + target - 1) / target);
-  const unsigned nb = unsigned(((ntiles + tpb - 1) / tpb + 7) / 8 * 8);  // multiple of 8 (XCD map)
+  const int64_t tpb = tiles_per_block(ntiles, target);
+  const unsigned nb = unsigned(blocks_for8(ntiles, tpb));  // multiple of 8 (XCD map)
   hipLaunchKernelGGL((k_ru_thin_bf16<C, K, R>), dim3(nb), dim3(256), RU::LDS, s, a,
                      static_cast<const __bf16*>(in), static_cast<const __bf16*>(w1p), b1,
                      static_cast<const __bf16*>(w2p), b2, static_cast<__bf16*>(h), static_cast<__bf16*>(out),
@@ -5374,18 +4957,10 @@ int launch_ru_thin(const Args& a, const void* in, const void* w1p, const float* 
 // walking an XCD-contiguous range of sample-aligned tiles
 template <int R, bool BWD>
 int64_t ru32_tiles_per_block(int64_t ntiles) {
-  static const int64_t slots = [] {
-    int dev = 0, cus = 0, per_cu = 0;
-    const size_t lds = BWD ? Ru32<R>::LDS_BWD : Ru32<R>::LDS_FWD;
-    const void* kern = BWD ? (const void*)k_ru32_bwd<R> : (const void*)k_ru32_fwd<R>;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, lds) != hipSuccess)
-      return int64_t(0);
-    return int64_t(cus) * per_cu / 8 * 8;
-  }();
+  static const int64_t slots = resident_blocks(BWD ? (const void*)k_ru32_bwd<R> : (const void*)k_ru32_fwd<R>, 256,
+                                               BWD ? Ru32<R>::LDS_BWD : Ru32<R>::LDS_FWD) / 8 * 8;
   const int64_t target = slots > 0 ? slots : 1024;
-  return std::max<int64_t>(1, (ntiles + target - 1) / target);
+  return tiles_per_block(ntiles, target);
 }
 
 template <int R>
@@ -5394,7 +4969,7 @@ int launch_ru32_fwd(const Args& a, const void* x, const void* w1p, const float* 
   const int64_t ntiles = (a.rows / a.T) * ((a.T + R - 1) / R);
   if (ntiles == 0) return SEL_OK;
   const int64_t tpb = ru32_tiles_per_block<R, false>(ntiles);
-  const unsigned nb = unsigned(((ntiles + tpb - 1) / tpb + 7) / 8 * 8);
+  const unsigned nb = unsigned(blocks_for8(ntiles, tpb));
   hipLaunchKernelGGL(k_ru32_fwd<R>, dim3(nb), dim3(256), Ru32<R>::LDS_FWD, s, a, static_cast<const __bf16*>(x),
                      static_cast<const __bf16*>(w1p), b1, static_cast<const __bf16*>(w2p), b2,
                      static_cast<__bf16*>(h), static_cast<__bf16*>(out), int(tpb), tune(15));
@@ -5407,17 +4982,10 @@ int launch_ru32_fwd4(const Args& a, const void* x, const void* w1p, const float*
   constexpr int R = 256;
   const int64_t ntiles = (a.rows / a.T) * ((a.T + R - 1) / R);
   if (ntiles == 0) return SEL_OK;
-  static const int64_t slots = [] {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ru32_fwd4<R>, 256, Ru32F4<R>::LDS) != hipSuccess)
-      return int64_t(0);
-    return int64_t(cus) * per_cu / 8 * 8;
-  }();
+  static const int64_t slots = resident_blocks((const void*)k_ru32_fwd4<R>, 256, Ru32F4<R>::LDS) / 8 * 8;
   const int64_t target = slots > 0 ? slots : 1024;
-  const int64_t tpb = std::max<int64_t>(1, (ntiles + target - 1) / target);
-  const unsigned nb = unsigned(((ntiles + tpb - 1) / tpb + 7) / 8 * 8);
+  const int64_t tpb = tiles_per_block(ntiles, target);
+  const unsigned nb = unsigned(blocks_for8(ntiles, tpb));
   hipLaunchKernelGGL(k_ru32_fwd4<R>, dim3(nb), dim3(256), Ru32F4<R>::LDS, s, a, static_cast<const __bf16*>(x),
                      static_cast<const __bf16*>(w1p), b1, static_cast<const __bf16*>(w2p), b2,
                      static_cast<__bf16*>(h), static_cast<__bf16*>(out), int(tpb));
@@ -5430,17 +4998,10 @@ int launch_ru64_fwd(const Args& a, const void* x, const void* w1p, const float* 
                     const float* b2, void* h, void* out, hipStream_t s) {
   const int64_t ntiles = (a.rows / a.T) * ((a.T + R - 1) / R);
   if (ntiles == 0) return SEL_OK;
-  static const int64_t slots = [] {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ru64_fwd<R>, 256, Ru64<R>::LDS) != hipSuccess)
-      return int64_t(0);
-    return int64_t(cus) * per_cu / 8 * 8;
-  }();
+  static const int64_t slots = resident_blocks((const void*)k_ru64_fwd<R>, 256, Ru64<R>::LDS) / 8 * 8;
   const int64_t target = tune(24) > 0 ? tune(24) : (slots > 0 ? slots : 1024);
-  const int64_t tpb = std::max<int64_t>(1, (ntiles + target - 1) / target);
-  const unsigned nb = unsigned(((ntiles + tpb - 1) / tpb + 7) / 8 * 8);
+  const int64_t tpb = tiles_per_block(ntiles, target);
+  const unsigned nb = unsigned(blocks_for8(ntiles, tpb));
   hipLaunchKernelGGL(k_ru64_fwd<R>, dim3(nb), dim3(256), Ru64<R>::LDS, s, a, static_cast<const __bf16*>(x),
                      static_cast<const __bf16*>(w1p), b1, static_cast<const __bf16*>(w2p), b2,
                      static_cast<__bf16*>(h), static_cast<__bf16*>(out), int(tpb));
@@ -5453,17 +5014,10 @@ int launch_ru64_bwd(const Args& a, const void* g, const void* h, const void* x, 
                     void* gh, void* gx, hipStream_t s) {
   const int64_t ntiles = (a.rows / a.T) * ((a.T + R - 1) / R);
   if (ntiles == 0) return SEL_OK;
-  static const int64_t slots = [] {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ru64_bwd<R>, 256, Ru64B<R>::LDS) != hipSuccess)
-      return int64_t(0);
-    return int64_t(cus) * per_cu / 8 * 8;
-  }();
+  static const int64_t slots = resident_blocks((const void*)k_ru64_bwd<R>, 256, Ru64B<R>::LDS) / 8 * 8;
   const int64_t target = slots > 0 ? slots : 1024;
-  const int64_t tpb = std::max<int64_t>(1, (ntiles + target - 1) / target);
-  const unsigned nb = unsigned(((ntiles + tpb - 1) / tpb + 7) / 8 * 8);
+  const int64_t tpb = tiles_per_block(ntiles, target);
+  const unsigned nb = unsigned(blocks_for8(ntiles, tpb));
   hipLaunchKernelGGL(k_ru64_bwd<R>, dim3(nb), dim3(256), Ru64B<R>::LDS, s, a, static_cast<const __bf16*>(g),
                      static_cast<const __bf16*>(h), static_cast<const __bf16*>(x), static_cast<const __bf16*>(wd1),
                      static_cast<const __bf16*>(wd2), static_cast<__bf16*>(gh), static_cast<__bf16*>(gx), int(tpb));
@@ -5477,7 +5031,7 @@ int launch_ru32_bwd(const Args& a, const void* g, const void* h, const void* x, 
   const int64_t ntiles = (a.rows / a.T) * ((a.T + R - 1) / R);
   if (ntiles == 0) return SEL_OK;
   const int64_t tpb = ru32_tiles_per_block<R, true>(ntiles);
-  const unsigned nb = unsigned(((ntiles + tpb - 1) / tpb + 7) / 8 * 8);
+  const unsigned nb = unsigned(blocks_for8(ntiles, tpb));
   hipLaunchKernelGGL(k_ru32_bwd<R>, dim3(nb), dim3(256), Ru32<R>::LDS_BWD, s, a, static_cast<const __bf16*>(g),
                      static_cast<const __bf16*>(h), static_cast<const __bf16*>(x), static_cast<const __bf16*>(wd1),
                      static_cast<const __bf16*>(wd2), static_cast<__bf16*>(gh), static_cast<__bf16*>(gx), int(tpb));
@@ -5488,17 +5042,10 @@ int launch_ru32_bwd(const Args& a, const void* g, const void* h, const void* x, 
 // fused 32-channel backward with the weight gradients: one block per partial
 template <int R>
 int ru32w_blocks(int64_t ntiles, int64_t& tpb) {
-  static const int64_t slots = [] {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ru32_bwdw<R>, 256, Ru32W<R>::LDS) != hipSuccess)
-      return int64_t(0);
-    return int64_t(cus) * per_cu / 8 * 8;
-  }();
+  static const int64_t slots = resident_blocks((const void*)k_ru32_bwdw<R>, 256, Ru32W<R>::LDS) / 8 * 8;
   const int64_t target = tune(35) > 0 ? tune(35) : (slots > 0 ? slots : 512);
-  tpb = std::max<int64_t>(1, (ntiles + target - 1) / target);
-  return int(((ntiles + tpb - 1) / tpb + 7) / 8 * 8);
+  tpb = tiles_per_block(ntiles, target);
+  return int(blocks_for8(ntiles, tpb));
 }
 
 template <int R>
@@ -5519,19 +5066,15 @@ int launch_ru32_bwdw(const Args& a, const void* g, const void* h, const void* x,
 // CU (its LDS planes), one partial per block
 template <int R, bool WG = true>
 int ru64w_blocks(int64_t ntiles, int64_t& tpb) {
-  static const int64_t slots = [] {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_ru64_bwdw<R, WG>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            int(Ru64W<R>::LDS)) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_ru64_bwdw<R, WG>, 512, Ru64W<R>::LDS) != hipSuccess)
-      return int64_t(0);
-    return int64_t(cus) * per_cu / 8 * 8;
-  }();
+  // (the occupancy query needs the kernel's 159 KB of dynamic LDS allowed first)
+  static const int64_t slots =
+      hipFuncSetAttribute((const void*)k_ru64_bwdw<R, WG>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                          int(Ru64W<R>::LDS)) == hipSuccess
+          ? resident_blocks((const void*)k_ru64_bwdw<R, WG>, 512, Ru64W<R>::LDS) / 8 * 8
+          : 0;
   const int64_t target = tune(40) > 0 ? tune(40) : (slots > 0 ? slots : 256);
-  tpb = std::max<int64_t>(1, (ntiles + target - 1) / target);
-  return int(((ntiles + tpb - 1) / tpb + 7) / 8 * 8);
+  tpb = tiles_per_block(ntiles, target);
+  return int(blocks_for8(ntiles, tpb));
 }
 
 template <int R, bool WG = true>
@@ -5571,16 +5114,8 @@ int launch_pw_t(const Args& a, const void* in, const void* wp, const float* bias
   using G = Pw<C, N>;
   if (a.rows == 0) return SEL_OK;
   // one round of resident workgroups, each over an equal contiguous row range
-  static const int64_t slots = [] {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pw_bf16<C, N, ELU, AUX, RES>, G::THREADS, G::LDS) !=
-            hipSuccess)
-      return int64_t(256);
-    return std::max<int64_t>(1, int64_t(cus) * std::max(per_cu, 1));
-  }();
-  const int64_t target = tune(43) > 0 ? tune(43) : slots;
+  static const int64_t round = resident_blocks((const void*)k_pw_bf16<C, N, ELU, AUX, RES>, G::THREADS, G::LDS);
+  const int64_t target = tune(43) > 0 ? tune(43) : (round > 0 ? round : 256);
   int64_t nb = std::min<int64_t>(target, (a.rows + G::R - 1) / G::R);
   // (a pass covers RB rows: a range of more rows takes several passes)
   const int64_t rpb = (a.rows + nb - 1) / nb;
@@ -5621,14 +5156,8 @@ bool ru_fused_ok(const Args& a) {
 template <typename TI, typename TO, int TR>
 int launch_c1(const Args& a, const void* in, const void* wp, const float* bias, const void* aux, const void* res,
               void* out, hipStream_t s) {
-  static const int64_t slots = [] {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_conv_c1<TI, TO, TR>, 256, 0) != hipSuccess)
-      return int64_t(4096);
-    return std::max<int64_t>(256, int64_t(cus) * per_cu);
-  }();
+  static const int64_t round = resident_blocks((const void*)k_conv_c1<TI, TO, TR>, 256, 0);
+  const int64_t slots = round > 0 ? std::max<int64_t>(256, round) : 4096;
   const int64_t blocks = std::min<int64_t>((a.rows / a.T) * ((a.T + TR - 1) / TR), tune(23) > 0 ? tune(23) : slots);
   if (blocks <= 0) return SEL_OK;
   hipLaunchKernelGGL((k_conv_c1<TI, TO, TR>), dim3(unsigned(blocks)), dim3(256), 0, s, a,
@@ -5638,57 +5167,86 @@ int launch_c1(const Args& a, const void* in, const void* wp, const float* bias, 
   return SEL_OK;
 }
 
+// Kernel family of a forward launch and the variant within it.  The order
+// pw -> thin -> c1 -> pipelined tiles -> generic is stated here alone:
+// sel_conv_fwd launches the pick, sel_conv_fwd_kernel_id reports it.
+enum Family {
+  kPw,        // k_pw_bf16; v = N
+  kThin,      // k_conv_thin_bf16; v = instance (thin_variant gives the E flag and tile rows)
+  kC1,        // k_conv_c1; v = tile rows
+  kFast,      // the pipelined bf16 kernels; v = fwd4_choice
+  kF32Tiles,  // k_conv_fwd_f32; v = BM (64: 64 x 64 tiles, 128: 128 x 32)
+  kGeneric    // k_conv_fwd; v = tile 1-6 (tune key 0 forces one)
+};
+struct FwdPick {
+  Family family;
+  int v;
+};
+
+bool c1_shape(const Args& a, int nmult) {
+  return a.C == 1 && a.N % nmult == 0 && a.N <= C1_NMAX && a.K <= C1_KMAX && (a.K - 1) * a.dil <= C1_HALO;
+}
+
+FwdPick fwd_pick(const Args& a, int in_dtype, int out_dtype) {
+  if (in_dtype == SEL_BF16) {
+    if (out_dtype == SEL_BF16) {
+      if (pw_ok(a)) return {kPw, a.N};
+      if (const int i = thin_index(a); i >= 0) return {kThin, i};
+    }
+    // tune key 44: 1 = the round-3 256-row tiles, 2 = 1024-row tiles
+    if (c1_shape(a, 8) && tune(3) == 0) return {kC1, tune(44) == 1 ? 256 : tune(44) == 2 ? 1024 : C1F_TR};
+    if (const int v = fwd4_choice(a, out_dtype == SEL_F32); v >= 0) return {kFast, v};
+    if (const int v = tune(0); v >= 1 && v <= 6) return {kGeneric, v};
+    return {kGeneric, a.N <= 32 ? 1 : (a.N <= 64 || a.K >= 5) ? 2 : a.rows >= 4096 ? 3 : 4};
+  }
+  if (out_dtype == SEL_F32 && tune(55) != 1) {  // tune key 55 = 1: the generic kernel
+    // single input channel: the streaming kernel with exact fp32 ELU
+    if (c1_shape(a, 4)) return {kC1, C1F_TR};
+    // sample-aligned fp32 tiles
+    if (a.C % FF_CK == 0 && a.N % 32 == 0 && a.K <= 8 && (a.K - 1) * a.dil <= FF_HALO)
+      return {kF32Tiles, a.N % 64 == 0 ? 64 : 128};
+  }
+  return {kGeneric, a.N <= 32 ? 1 : 4};
+}
+
 template <typename TI, typename TO>
 int dispatch_fwd(const Args& a, const void* in, const void* wp, const float* bias, const void* aux,
                  const void* res, void* out, hipStream_t s) {
-  if constexpr (sizeof(TI) == 2 && sizeof(TO) == 2) {
-    if (pw_ok(a))
-      return a.N == 256 ? launch_pw<256, 256>(a, in, wp, bias, aux, res, out, s)
-                        : launch_pw<128, 128>(a, in, wp, bias, aux, res, out, s);
-    const int rc = dispatch_thin(a, in, wp, bias, aux, res, out, s);
-    if (rc != kNotThin) return rc;
-  }
+  const FwdPick p = fwd_pick(a, sizeof(TI) == 4 ? SEL_F32 : SEL_BF16, sizeof(TO) == 4 ? SEL_F32 : SEL_BF16);
   if constexpr (sizeof(TI) == 2) {
-    if (a.C == 1 && a.N % 8 == 0 && a.N <= C1_NMAX && a.K <= C1_KMAX && (a.K - 1) * a.dil <= C1_HALO &&
-        tune(3) == 0)
-      return tune(44) == 1   ? launch_c1<TI, TO, 256>(a, in, wp, bias, aux, res, out, s)
-             : tune(44) == 2 ? launch_c1<TI, TO, 1024>(a, in, wp, bias, aux, res, out, s)
+    switch (p.family) {
+      case kPw:
+        return a.N == 256 ? launch_pw<256, 256>(a, in, wp, bias, aux, res, out, s)
+                          : launch_pw<128, 128>(a, in, wp, bias, aux, res, out, s);
+      case kThin: {
+        int rows = 0;
+        const bool e = thin_variant(a, aux || res, rows);
+        return launch_thin_variant(p.v, e, rows, a, in, wp, bias, aux, res, out, s);
+      }
+      case kC1:
+        return p.v == 256    ? launch_c1<TI, TO, 256>(a, in, wp, bias, aux, res, out, s)
+               : p.v == 1024 ? launch_c1<TI, TO, 1024>(a, in, wp, bias, aux, res, out, s)
                              : launch_c1<TI, TO, C1F_TR>(a, in, wp, bias, aux, res, out, s);
-    const int v = tune(0);
-    const bool fast = (a.C % CK) == 0 && (a.K - 1) * a.dil <= F4_HALOMAX && a.K <= 8 && (v == 0 || v > 20);
-    if (fast) {
-      if (a.K == 1) return fwd4_variant<1, TO>(v, a, in, wp, bias, aux, res, out, s);
-      if (a.K <= 3) return fwd4_variant<3, TO>(v, a, in, wp, bias, aux, res, out, s);
-      return fwd4_variant<8, TO>(v, a, in, wp, bias, aux, res, out, s);
+      case kFast:
+        if (a.K == 1) return fwd4_variant<1, TO>(p.v, a, in, wp, bias, aux, res, out, s);
+        if (a.K <= 3) return fwd4_variant<3, TO>(p.v, a, in, wp, bias, aux, res, out, s);
+        return fwd4_variant<8, TO>(p.v, a, in, wp, bias, aux, res, out, s);
+      default: break;
     }
-    switch (v) {
-      case 1: return launch_fwd<TI, TO, 128, 32>(a, in, wp, bias, aux, res, out, s);
+    switch (p.v) {  // kGeneric
       case 2: return launch_fwd<TI, TO, 128, 64>(a, in, wp, bias, aux, res, out, s);
       case 3: return launch_fwd<TI, TO, 128, 128>(a, in, wp, bias, aux, res, out, s);
-      case 4: return launch_fwd<TI, TO, 64, 64>(a, in, wp, bias, aux, res, out, s);
       case 5: return launch_fwd<TI, TO, 256, 32>(a, in, wp, bias, aux, res, out, s);
       case 6: return launch_fwd<TI, TO, 256, 64>(a, in, wp, bias, aux, res, out, s);
       default: break;
     }
+  } else {
+    if (p.family == kC1) return launch_c1<TI, TO, C1F_TR>(a, in, wp, bias, aux, res, out, s);
+    if (p.family == kF32Tiles)
+      return p.v == 64 ? launch_fwd_f32<64, 64>(a, in, wp, bias, aux, res, out, s)
+                       : launch_fwd_f32<128, 32>(a, in, wp, bias, aux, res, out, s);
   }
-  if (sizeof(TI) == 4) {
-    if constexpr (sizeof(TO) == 4) {
-      // single input channel: the streaming kernel with exact fp32 ELU (tune key 55 = 1: generic)
-      if (a.C == 1 && a.N % 4 == 0 && a.N <= C1_NMAX && a.K <= C1_KMAX && (a.K - 1) * a.dil <= C1_HALO &&
-          tune(55) != 1)
-        return launch_c1<TI, TO, C1F_TR>(a, in, wp, bias, aux, res, out, s);
-      // sample-aligned fp32 tiles (tune key 55 = 1: the generic kernel)
-      if (a.C % FF_CK == 0 && a.N % 32 == 0 && a.K <= 8 && (a.K - 1) * a.dil <= FF_HALO && tune(55) != 1) {
-        if (a.N % 64 == 0) return launch_fwd_f32<64, 64>(a, in, wp, bias, aux, res, out, s);
-        return launch_fwd_f32<128, 32>(a, in, wp, bias, aux, res, out, s);
-      }
-    }
-    if (a.N <= 32) return launch_fwd<TI, TO, 128, 32>(a, in, wp, bias, aux, res, out, s);
-    return launch_fwd<TI, TO, 64, 64>(a, in, wp, bias, aux, res, out, s);
-  }
-  if (a.N <= 32) return launch_fwd<TI, TO, 128, 32>(a, in, wp, bias, aux, res, out, s);
-  if (a.N <= 64 || a.K >= 5) return launch_fwd<TI, TO, 128, 64>(a, in, wp, bias, aux, res, out, s);
-  if (a.rows >= 4096) return launch_fwd<TI, TO, 128, 128>(a, in, wp, bias, aux, res, out, s);
+  if (p.v == 1) return launch_fwd<TI, TO, 128, 32>(a, in, wp, bias, aux, res, out, s);
   return launch_fwd<TI, TO, 64, 64>(a, in, wp, bias, aux, res, out, s);
 }
 
@@ -5879,10 +5437,7 @@ int dconv_ws_fwd(const sel_dconv_desc* d, const void* x, const void* wp, const f
   a.epi = 1;
   a.act = d->act;
   a.slope = d->slope;
-  if (dconv_ws8_ok(d)) {
-    if (d->K == 2) return launch_ws8<2, __bf16, 256, 256, 32>(a, x, wp, bias, aux, res, out, s);
-    return launch_ws8<5, __bf16, 256, 256, 32>(a, x, wp, bias, aux, res, out, s);
-  }
+  if (dconv_ws8_ok(d)) return launch_ws8<2, __bf16, 256, 256, 32>(a, x, wp, bias, aux, res, out, s);  // K == 2
   switch (d->K) {
     case 2: return launch_ws<2, __bf16>(a, x, wp, bias, aux, res, out, s);
     case 3: return launch_ws<3, __bf16>(a, x, wp, bias, aux, res, out, s);
@@ -5898,14 +5453,15 @@ extern "C" {
 int sel_conv_fwd_kernel_id(const sel_conv_desc* d, int in_dtype, int out_dtype, int has_epilogue) {
   if (!d || in_dtype != SEL_BF16 || check_desc(d) != SEL_OK) return -1;
   const Args a = to_args(d);
-  if (out_dtype == SEL_BF16 && pw_ok(a)) return 930000000 + a.N;  // pointwise: 9.3e8 + N
-  if (out_dtype == SEL_BF16 && thin_ok(a)) {  // thin: 1e9 + E*5e8 + ((R/32*1000 + C)*1000 + N)*10 + K
+  const FwdPick p = fwd_pick(a, in_dtype, out_dtype);
+  if (p.family == kPw) return 930000000 + a.N;  // pointwise: 9.3e8 + N
+  if (p.family == kThin) {  // thin: 1e9 + E*5e8 + ((R/32*1000 + C)*1000 + N)*10 + K
     int r = 0;
     const bool e = thin_variant(a, has_epilogue != 0, r);
     return 1000000000 + (e ? 500000000 : 0) + ((r / 32 * 1000 + a.C) * 1000 + a.N) * 10 + a.K;
   }
-  const int v = fwd4_choice(a, out_dtype == SEL_F32);
-  if (v < 0) return -1;
+  if (p.family != kFast) return -1;
+  const int v = p.v;
   // warp-specialised kernels: 9e8 + K (12 waves), 9.1e8 + K (eight waves, 512 x 128)
   if (v == 27) return 900000000 + a.K;
   if (v == 28) return 910000000 + a.K;
@@ -6346,150 +5902,6 @@ int sel_wgrad_finish_many(const sel_wgrad_job* jobs, int njobs, sel_stream_t str
       SEL_LAUNCH_CHECK();
     }
   }
-  return SEL_OK;
-}
-
-int sel_pack_weight(int kind, const float* w, int cout, int cin, int k, int stride, int dtype, void* wpack,
-
-                    sel_stream_t stream) {
-  SEL_REQUIRE(kind >= SEL_PACK_FWD && kind <= SEL_PACK_CONVT, SEL_ERR_ARG, "bad pack kind");
-  SEL_REQUIRE(kind == SEL_PACK_FWD || k == 2 * stride, SEL_ERR_UNSUPPORTED,
-              "strided/transposed conv needs kernel_size == 2*stride (got %d, %d)", k, stride);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int64_t total = kind == SEL_PACK_FWD ? int64_t(cout) * k * cin
-                        : kind == SEL_PACK_FWD_STRIDED ? int64_t(cout) * 3 * stride * cin
-                                                       : int64_t(stride) * cout * 2 * cin;
-  dim3 grid(unsigned(std::min<int64_t>(4096, (total + 255) / 256)));
-  if (dtype == SEL_F32)
-    hipLaunchKernelGGL(k_pack<float>, grid, dim3(256), 0, s, kind, w, cout, cin, k, stride,
-                       static_cast<float*>(wpack));
-  else
-    hipLaunchKernelGGL(k_pack<__bf16>, grid, dim3(256), 0, s, kind, w, cout, cin, k, stride,
-                       static_cast<__bf16*>(wpack));
-  SEL_LAUNCH_CHECK();
-  return SEL_OK;
-}
-
-int sel_pack_many(const sel_pack_job* jobs, int njobs, int64_t total, int dtype, sel_stream_t stream) {
-  SEL_REQUIRE(jobs && njobs > 0 && total > 0, SEL_ERR_ARG, "empty pack job table");
-  // (the job table is device memory: each job's element count is checked < 2^31
-  // by the host binding, sel/convops.py PackCache._refresh)
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  dim3 grid(unsigned(std::min<int64_t>(8192, (2 * total + 255) / 256)));
-  if (dtype == SEL_F32)
-    hipLaunchKernelGGL(k_pack_many<float>, grid, dim3(256), 0, s, jobs, njobs, total);
-  else
-    hipLaunchKernelGGL(k_pack_many<__bf16>, grid, dim3(256), 0, s, jobs, njobs, total);
-  SEL_LAUNCH_CHECK();
-  return SEL_OK;
-}
-
-int sel_pack_many_host(const sel_pack_job* jobs, int njobs, int64_t total, int dtype, sel_stream_t stream) {
-  using namespace sel::conv;
-  SEL_REQUIRE(jobs && njobs > 0 && total > 0, SEL_ERR_ARG, "empty pack job table");
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  for (int j0 = 0; j0 < njobs; j0 += PM_MAXJ) {
-    PackJobs pj{};
-    pj.n = std::min(PM_MAXJ, njobs - j0);
-    for (int j = 0; j < pj.n; ++j) {
-      pj.j[j] = jobs[j0 + j];
-      SEL_REQUIRE(pj.j[j].offset >= 0 && pj.j[j].offset < total && (j == 0 || pj.j[j].offset > pj.j[j - 1].offset),
-                  SEL_ERR_ARG, "pack jobs must have increasing offsets within total");
-    }
-    // tiled kernel (k_pack_tiles) unless a job's taps exceed its tile (K > 8)
-    // or tune key 60 = 1 asks for the per-element form
-    PackTiles pt{};
-    bool tiled = tune(60) != 1;
-    int64_t tiles = 0;
-    pt.n = pj.n;
-    for (int j = 0; j < pj.n && tiled; ++j) {
-      const sel_pack_job& J = pj.j[j];
-      const int64_t N = J.kind == SEL_PACK_CONVT ? int64_t(J.stride) * J.cout : J.cout;
-      const int64_t KP = J.kind == SEL_PACK_FWD ? J.k : J.kind == SEL_PACK_FWD_STRIDED ? 3 : 2;
-      const int64_t CP = J.kind == SEL_PACK_FWD_STRIDED ? int64_t(J.stride) * J.cin : J.cin;
-      if (KP > PT_KMAX) tiled = false;
-      pt.j[j] = J;
-      pt.tstart[j] = int(tiles);
-      tiles += ((N + PT_T - 1) / PT_T) * ((CP + PT_T - 1) / PT_T);
-    }
-    pt.tstart[pt.n] = int(tiles);
-    if (tiled && tiles > 0 && tiles < (int64_t(1) << 31)) {
-      if (dtype == SEL_F32)
-        hipLaunchKernelGGL((k_pack_tiles<float, 1024>), dim3(unsigned(tiles)), dim3(1024), 0, s, pt);
-      else
-        hipLaunchKernelGGL((k_pack_tiles<__bf16, 1024>), dim3(unsigned(tiles)), dim3(1024), 0, s, pt);
-      SEL_LAUNCH_CHECK();
-      continue;
-    }
-    const int64_t lo = pj.j[0].offset;
-    const int64_t hi = j0 + pj.n < njobs ? jobs[j0 + pj.n].offset : total;
-    dim3 grid(unsigned(std::min<int64_t>(8192, (2 * (hi - lo) + 255) / 256)));
-    if (dtype == SEL_F32)
-      hipLaunchKernelGGL(k_pack_many_arg<float>, grid, dim3(256), 0, s, pj, lo, hi, total);
-    else
-      hipLaunchKernelGGL(k_pack_many_arg<__bf16>, grid, dim3(256), 0, s, pj, lo, hi, total);
-    SEL_LAUNCH_CHECK();
-  }
-  return SEL_OK;
-}
-
-int sel_pack_dgrad(const void* wpack, int N, int K, int C, int dtype, void* wd, sel_stream_t stream) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int64_t total = int64_t(N) * K * C;
-  dim3 grid(unsigned(std::min<int64_t>(4096, (total + 255) / 256)));
-  if (dtype == SEL_F32)
-    hipLaunchKernelGGL(k_pack_dgrad<float>, grid, dim3(256), 0, s, static_cast<const float*>(wpack), N, K, C,
-                       static_cast<float*>(wd));
-  else
-    hipLaunchKernelGGL(k_pack_dgrad<__bf16>, grid, dim3(256), 0, s, static_cast<const __bf16*>(wpack), N, K,
-                       C, static_cast<__bf16*>(wd));
-  SEL_LAUNCH_CHECK();
-  return SEL_OK;
-}
-
-int sel_unpack_wgrad(int kind, const float* gwpack, int cout, int cin, int k, int stride, float* gw,
-                     sel_stream_t stream) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const int64_t total = int64_t(cout) * cin * (kind == SEL_PACK_FWD ? k : 2 * stride);
-  dim3 grid(unsigned(std::min<int64_t>(4096, (total + 255) / 256)));
-  hipLaunchKernelGGL(k_unpack, grid, dim3(256), 0, s, kind, gwpack, cout, cin, k, stride, gw);
-  SEL_LAUNCH_CHECK();
-  return SEL_OK;
-}
-
-int sel_conv_replicate_fix(const sel_conv_desc* d, int dtype, const void* gout, const void* wpack, void* gin,
-                           sel_stream_t stream) {
-  if (int rc = check_desc(d)) return rc;
-  const Args a = to_args(d);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  const unsigned nb = unsigned(d->rows / d->T);
-  if (nb == 0) return SEL_OK;
-  const dim3 grid(nb, unsigned((d->C + 63) / 64));
-  if (dtype == SEL_F32)
-    hipLaunchKernelGGL(k_replicate_fix<float>, grid, dim3(1024), 0, s, a, static_cast<const float*>(gout),
-                       static_cast<const float*>(wpack), static_cast<float*>(gin));
-  else
-    hipLaunchKernelGGL(k_replicate_fix<__bf16>, grid, dim3(1024), 0, s, a, static_cast<const __bf16*>(gout),
-                       static_cast<const __bf16*>(wpack), static_cast<__bf16*>(gin));
-  SEL_LAUNCH_CHECK();
-  return SEL_OK;
-}
-
-int sel_cast(const void* src, int src_dtype, void* dst, int dst_dtype, int64_t n, sel_stream_t stream) {
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (n <= 0) return SEL_OK;
-  dim3 grid(unsigned(std::min<int64_t>(8192, (n + 255) / 256)));
-  if (src_dtype == SEL_F32 && dst_dtype == SEL_BF16)
-    hipLaunchKernelGGL((k_cast<float, __bf16>), grid, dim3(256), 0, s, static_cast<const float*>(src),
-                       static_cast<__bf16*>(dst), n);
-  else if (src_dtype == SEL_BF16 && dst_dtype == SEL_F32)
-    hipLaunchKernelGGL((k_cast<__bf16, float>), grid, dim3(256), 0, s, static_cast<const __bf16*>(src),
-                       static_cast<float*>(dst), n);
-  else {
-    set_error("unsupported cast %d -> %d", src_dtype, dst_dtype);
-    return SEL_ERR_UNSUPPORTED;
-  }
-  SEL_LAUNCH_CHECK();
   return SEL_OK;
 }
 

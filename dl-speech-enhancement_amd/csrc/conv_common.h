@@ -1,4 +1,5 @@
-// Helpers shared by the conv-stack translation units (conv.hip, conv_wss.hip).
+// Helpers shared by the conv-stack translation units (conv.hip, conv_wss.hip,
+// conv_pack.hip).
 #pragma once
 #include "sel_common.h"
 
@@ -104,6 +105,9 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 namespace sel {
 namespace conv {
+// conv.hip: descriptor check and its kernel-argument form
+int check_desc(const sel_conv_desc* d);
+Args to_args(const sel_conv_desc* d);
 // conv_wss.hip: sample-tile warp-specialised kernel (T <= 400)
 bool wss_geometry(const Args& a, int& S, int& tm, int& BN);  // strips per tile, tile rows, channels
 bool wss_geometry(const Args& a, int& S, int& tm);

@@ -63,6 +63,29 @@ __device__ __forceinline__ uint4 ru_bload(__amdgpu_buffer_rsrc_t rs, int byte_of
 // real load).
 inline bool ru_region_ok(int64_t bytes) { return bytes >= 0 && bytes <= RU_OOB; }
 
+// One resident round of workgroups for the persistent tile-walking kernels:
+// CUs times the kernel's occupancy at `threads` per block and `lds` dynamic
+// bytes, or 0 when a query fails (every caller has its own fallback target,
+// rounding and tune override; callers cache the result in a function-local
+// static, one per kernel instance).
+inline int64_t resident_blocks(const void* kern, int threads, size_t lds) {
+  int dev = 0, cus = 0, per_cu = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds) != hipSuccess)
+    return 0;
+  return int64_t(cus) * per_cu;
+}
+// tiles each workgroup walks so that `target` workgroups cover ntiles, and the
+// grid that takes: ceil(ntiles / tpb), or that rounded up to a multiple of 8
+// (the XCD map of the tile-walking kernels)
+inline int64_t tiles_per_block(int64_t ntiles, int64_t target) {
+  const int64_t tpb = (ntiles + target - 1) / target;
+  return tpb > 1 ? tpb : 1;
+}
+inline int64_t blocks_for(int64_t ntiles, int64_t tpb) { return (ntiles + tpb - 1) / tpb; }
+inline int64_t blocks_for8(int64_t ntiles, int64_t tpb) { return (blocks_for(ntiles, tpb) + 7) / 8 * 8; }
+
 }  // namespace sel
 
 #define SEL_REQUIRE(cond, code, ...)      \

@@ -1593,18 +1593,6 @@ unsigned frame_grid(int64_t nframes, int& iters, int64_t slots = 0, int fpb = Ge
 // grid of the last SEL_FRAME_DISPATCH on this thread (per-block partial counts)
 thread_local unsigned t_last_frame_grid = 0;
 
-// resident-block capacity of a frame kernel at `lds` bytes per block (cached
-// per call site by the dispatch macro)
-template <typename KerT>
-int64_t frame_slots(KerT ker, size_t lds, int block = 256) {
-  int dev = 0, cus = 0, per_cu = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ker, block, lds) != hipSuccess)
-    return 0;
-  return int64_t(cus) * per_cu;
-}
-
 // dispatch helper: one template kernel family over LOGN in [8, 11]; the kernel's
 // trailing arguments are (iters, ...EXTRA); EXTRA_FLOATS = per-frame LDS floats
 // beyond the spectrum slots
@@ -1613,7 +1601,7 @@ int64_t frame_slots(KerT ker, size_t lds, int block = 256) {
     using G = Geo<L>;                                                                         \
     int iters;                                                                                \
     const size_t lds = size_t(G::FPB) * (G::PADN * sizeof(float2) + size_t(extra) * sizeof(float)); \
-    static const int64_t slots = frame_slots(KER<L>, lds);                                    \
+    static const int64_t slots = resident_blocks((const void*)KER<L>, 256, lds);                    \
     const unsigned grid = frame_grid<L>(nframes, iters, slots);                               \
     t_last_frame_grid = grid;                                                                 \
     if (grid) hipLaunchKernelGGL(KER<L>, dim3(grid), dim3(256), lds, stream, __VA_ARGS__, iters); \
@@ -1681,7 +1669,7 @@ int sel_stft_mag_fwd(const float* x, int64_t B, int64_t T, int n_fft, int hop, i
       constexpr int BS = mag_block<L>(), FPBB = BS / Geo<L>::LPF;                                         \
       int iters;                                                                                          \
       const size_t lds = size_t(FPBB) * Geo<L>::PADN * sizeof(float2);                                    \
-      static const int64_t slots = frame_slots(k_stft_mag_fwd<L, BS>, lds, BS);                           \
+      static const int64_t slots = resident_blocks((const void*)k_stft_mag_fwd<L, BS>, BS, lds);          \
       const unsigned grid = frame_grid<L>(nf, iters, slots, FPBB);                                        \
       if (grid) hipLaunchKernelGGL((k_stft_mag_fwd<L, BS>), dim3(grid), dim3(BS), lds, s, x, a, window, pow_floor, \
                                    mag, iters);                                                           \
@@ -1828,7 +1816,7 @@ int sel_logmel_fwd(const float* x, int64_t B, int64_t T, int n_fft, int hop, int
       using G = Geo<L>;                                                                                 \
       int iters;                                                                                        \
       const size_t lds = size_t(G::FPB) * G::PADN * sizeof(float2) + mel_lds_bytes(n_mels);             \
-      const unsigned grid = frame_grid<L>(nf, iters, frame_slots(k_logmel_fwd<L>, lds));               \
+      const unsigned grid = frame_grid<L>(nf, iters, resident_blocks((const void*)k_logmel_fwd<L>, 256, lds)); \
       if (grid) hipLaunchKernelGGL(k_logmel_fwd<L>, dim3(grid), dim3(256), lds, s, x, a, window, ma, out, iters); \
     } break;
     SEL_LOGMEL_FWD_CASE(8)
@@ -1902,7 +1890,7 @@ int sel_mel_l1_fwd_grad(const float* x, const float* y, int64_t B, int64_t T, in
       int iters;                                                                                        \
       const size_t lds = size_t(G::FPB) * (G::PADN * sizeof(float2) + size_t(glin) * sizeof(float)) +   \
                          mel_lds_bytes(n_mels) + size_t(G::M + 1) * sizeof(int2);                       \
-      grid = frame_grid<L>(nf, iters, frame_slots(k_mel_l1<L>, lds));                                   \
+      grid = frame_grid<L>(nf, iters, resident_blocks((const void*)k_mel_l1<L>, 256, lds));             \
       if (grid)                                                                                         \
         hipLaunchKernelGGL(k_mel_l1<L>, dim3(grid), dim3(256), lds, s, x, y, a, window, ma,             \
                            reinterpret_cast<const int2*>(krange), float(1.0 / n), part, slab, iters, glin); \
@@ -1953,7 +1941,7 @@ int sel_logmel_bwd(const float* x, int64_t B, int64_t T, int n_fft, int hop, int
       int iters;                                                                                        \
       const size_t lds = size_t(G::FPB) * (G::PADN * sizeof(float2) + size_t(glin) * sizeof(float)) +   \
                          mel_lds_bytes(n_mels);                                                         \
-      const unsigned grid = frame_grid<L>(nf, iters, frame_slots(k_logmel_bwd<L>, lds));               \
+      const unsigned grid = frame_grid<L>(nf, iters, resident_blocks((const void*)k_logmel_bwd<L>, 256, lds)); \
       if (grid)                                                                                         \
         hipLaunchKernelGGL(k_logmel_bwd<L>, dim3(grid), dim3(256), lds, s, x, a, window, ma,           \
                            reinterpret_cast<const int2*>(krange), g_out, ref, g_scale, g_mul, slab, iters, \

@@ -1,7 +1,7 @@
 """Parity of the C3 (BASELINE configs[2]) bf16 path at the bench's own size.
 
 1. Every bf16 tile variant of the MFMA conv primitive (tune key 0 = 21..27,
-   conv.hip fwd4_variant; 27 = the warp-specialised k_conv_ws_bf16, 28 / 29 =
+   conv.hip fwd4_choice; 27 = the warp-specialised k_conv_ws_bf16, 28 / 29 =
    its eight-wave forms k_conv_ws8 (512 x 128 tiles of 128 x 64 wave tiles /
    256 x 128 of 64 x 64), bit-identical to 27 where they apply; 30 = the
    sample-tile kernel k_conv_wss of conv_wss.hip, whole 400-row samples x 64
