@@ -20,6 +20,12 @@
 //   k_rvq_step_any: every accepted shape.  256 threads, 4 codes per thread per
 //     pass of 1024 codes, columns read inside the d loop.
 // No atomics, no workspace; idx is written per stage, so S is unbounded.
+//
+// Wire format (include/sel.h, wire version 1): both quantize kernels have a
+// WIRE instance (sel_rvq_step_wire) in which wave 0, where the pick already
+// lives, also shifts it into the row's bit-packed record and stores the bytes
+// that fill; the lookup has one (sel_rvq_lookup_wire_step) that takes its ids
+// out of such records instead of an int64 buffer.  A row owns its bytes.
 #include <algorithm>
 
 #include "sel_common.h"
@@ -53,14 +59,57 @@ __device__ __forceinline__ int64_t active_rows(const int32_t* n_active, int cap,
   return n_active ? int64_t(min(max(*n_active, 0), cap)) * T : rows;
 }
 
+// ---- the packed record of a row: field s in bits [s * bits, (s + 1) * bits), bit i of the
+// record = bit i % 8 of byte i / 8; ceil(S * bits / 8) bytes, the pad bits zero ----
+__host__ __device__ __forceinline__ int wire_bits(int K) {
+  int b = 1;
+  while (b < 31 && (int64_t(1) << b) < K) ++b;
+  return b;
+}
+
+template <bool WIRE> struct WireDst {};  // a kernel argument: empty unless the instance packs
+template <> struct WireDst<true> {
+  uint8_t* wire;  // (rows, frame_bytes)
+  int64_t frame_bytes;
+  int bits;
+};
+
+// The writer's state, the same in every lane of wave 0: at most 7 + 31 bits are
+// ever held, whole bytes leave as they fill, so S is unbounded here too.
+template <bool WIRE> struct WirePack {
+  __device__ __forceinline__ WirePack(const WireDst<WIRE>&, int64_t) {}
+};
+template <> struct WirePack<true> {
+  uint8_t* p;    // the record's next byte
+  uint64_t acc;  // fields not yet stored, lowest bit first
+  int fill;      // bits in acc: < 8 between stages
+  int bits;
+  __device__ __forceinline__ WirePack(const WireDst<true>& w, int64_t row)
+      : p(w.wire + row * w.frame_bytes), acc(0), fill(0), bits(w.bits) {}
+  __device__ __forceinline__ void put(int k, bool writer) {
+    acc |= uint64_t(uint32_t(k)) << fill;
+    fill += bits;
+    while (fill >= 8) {
+      if (writer) *p = uint8_t(acc);
+      ++p;
+      acc >>= 8;
+      fill -= 8;
+    }
+  }
+  __device__ __forceinline__ void finish(bool writer) {  // the last partial byte, zero-padded
+    if (fill > 0 && writer) *p = uint8_t(acc);
+  }
+};
+
 // What both quantize kernels do once every thread holds its best (distance, code):
 // the block argmin (NW waves), then the first wave applies the pick to the row.
 // A row whose distances are all NaN keeps the initial 0x7fffffff: the pick is
 // forced to code 0 before anything is read through it.
-template <int NW>
+template <int NW, bool WIRE>
 __device__ __forceinline__ void pick_and_update(float bd, int bk, int D, int K, const float* __restrict__ E,
                                                 float* res, float* acc, float* red_d, int* red_k,
-                                                int64_t* __restrict__ idx_out, int64_t idx_off) {
+                                                int64_t* __restrict__ idx_out, int64_t idx_off,
+                                                WirePack<WIRE>& pack) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   wave_argmin(bd, bk);
   if (lane == 0) {
@@ -73,7 +122,12 @@ __device__ __forceinline__ void pick_and_update(float bd, int bk, int D, int K, 
     int k0 = lane < NW ? red_k[lane] : 0x7fffffff;
     wave_argmin(d0, k0);
     if (unsigned(k0) >= unsigned(K)) k0 = 0;
-    if (lane == 0) *idx_out = int64_t(k0) + idx_off;
+    if constexpr (WIRE) {  // idx is optional next to the record
+      if (lane == 0 && idx_out) *idx_out = int64_t(k0) + idx_off;
+      pack.put(k0, lane == 0);
+    } else {
+      if (lane == 0) *idx_out = int64_t(k0) + idx_off;
+    }
     for (int d = lane; d < D; d += 64) {
       const float q = E[int64_t(d) * K + k0];
       const float rv = res[d];
@@ -86,10 +140,12 @@ __device__ __forceinline__ void pick_and_update(float bd, int bk, int D, int K, 
   __syncthreads();
 }
 
+template <bool WIRE>
 __global__ __launch_bounds__(COL_T) void k_rvq_step_col(const float* __restrict__ z, int64_t rows, int T,
                                                         const float* __restrict__ embeds, int S,
                                                         const int32_t* __restrict__ n_active, int cap, int flatten,
-                                                        int64_t* __restrict__ idx, float* __restrict__ zq) {
+                                                        int64_t* __restrict__ idx, float* __restrict__ zq,
+                                                        WireDst<WIRE> wire) {
   constexpr int D = COL_D, K = COL_K, NW = COL_T / 64, C = COL_K / COL_T;
   __shared__ __align__(16) float res[D];
   __shared__ float acc[D];
@@ -99,6 +155,7 @@ __global__ __launch_bounds__(COL_T) void k_rvq_step_col(const float* __restrict_
   const int64_t row = blockIdx.x;
   if (row >= active_rows(n_active, cap, T, rows)) return;  // block-uniform
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  WirePack<WIRE> pack(wire, row);
 
   // One stage's codebook as a buffer resource: a load is then one VGPR byte
   // offset (the thread's code pair) plus a scalar offset (the row d) -- 64
@@ -164,16 +221,20 @@ __global__ __launch_bounds__(COL_T) void k_rvq_step_col(const float* __restrict_
         bk = C * tid + j;
       }
     }
-    pick_and_update<NW>(bd, bk, D, K, E, res, acc, red_d, red_k, idx + int64_t(s) * rows + row,
-                        flatten ? int64_t(s) * K : 0);
+    pick_and_update<NW, WIRE>(bd, bk, D, K, E, res, acc, red_d, red_k,
+                              WIRE && !idx ? nullptr : idx + int64_t(s) * rows + row, flatten ? int64_t(s) * K : 0,
+                              pack);
   }
+  if constexpr (WIRE) pack.finish(tid == 0);
   if (zq && tid < D) zq[row * D + tid] = acc[tid];
 }
 
+template <bool WIRE>
 __global__ __launch_bounds__(ANY_T) void k_rvq_step_any(const float* __restrict__ z, int64_t rows, int T, int D,
                                                         const float* __restrict__ embeds, int S, int K,
                                                         const int32_t* __restrict__ n_active, int cap, int flatten,
-                                                        int64_t* __restrict__ idx, float* __restrict__ zq) {
+                                                        int64_t* __restrict__ idx, float* __restrict__ zq,
+                                                        WireDst<WIRE> wire) {
   constexpr int NW = ANY_T / 64;
   __shared__ float res[MAXD];
   __shared__ float acc[MAXD];
@@ -183,6 +244,7 @@ __global__ __launch_bounds__(ANY_T) void k_rvq_step_any(const float* __restrict_
   const int64_t row = blockIdx.x;
   if (row >= active_rows(n_active, cap, T, rows)) return;  // block-uniform
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  WirePack<WIRE> pack(wire, row);
   for (int d = tid; d < D; d += ANY_T) {
     res[d] = z[row * D + d];
     acc[d] = 0.f;
@@ -231,9 +293,11 @@ __global__ __launch_bounds__(ANY_T) void k_rvq_step_any(const float* __restrict_
         }
       }
     }
-    pick_and_update<NW>(bd, bk, D, K, E, res, acc, red_d, red_k, idx + int64_t(s) * rows + row,
-                        flatten ? int64_t(s) * K : 0);
+    pick_and_update<NW, WIRE>(bd, bk, D, K, E, res, acc, red_d, red_k,
+                              WIRE && !idx ? nullptr : idx + int64_t(s) * rows + row, flatten ? int64_t(s) * K : 0,
+                              pack);
   }
+  if constexpr (WIRE) pack.finish(tid == 0);
   if (zq)
     for (int d = tid; d < D; d += ANY_T) zq[row * D + d] = acc[d];
 }
@@ -255,9 +319,20 @@ struct LookupArgs {
 
 constexpr int LK_T = 256;
 
+// WIRE: the ids come out of the rows' packed records (LookupArgs::idx is unused,
+// ncodes = S * K): a thread streams its row's bytes through the accumulator the
+// packer uses, byte loads only, so the buffer may have any alignment.
+template <bool WIRE> struct WireSrc {};
+template <> struct WireSrc<true> {
+  const uint8_t* wire;  // (rows, frame_bytes)
+  int64_t* idx_out;     // (S, rows) flattened ids, -1 for a refused field; may be null
+  int64_t frame_bytes;
+  int K, bits;
+};
+
 // V = 4: one thread per 4 channels (D % 4 == 0, 16-byte aligned operands); V = 1: per channel
-template <typename TO, int V>
-__global__ __launch_bounds__(LK_T) void k_rvq_lookup_step(LookupArgs a, TO* __restrict__ out) {
+template <typename TO, int V, bool WIRE>
+__global__ __launch_bounds__(LK_T) void k_rvq_lookup_step(LookupArgs a, TO* __restrict__ out, WireSrc<WIRE> w) {
   const int per_row = a.D / V;
   const int64_t live = active_rows(a.n_active, a.cap, a.T, a.rows);
   const int64_t i0 = int64_t(blockIdx.x) * LK_T;
@@ -270,8 +345,30 @@ __global__ __launch_bounds__(LK_T) void k_rvq_lookup_step(LookupArgs a, TO* __re
 #pragma unroll
   for (int j = 0; j < V; ++j) acc[j] = 0.f;
   bool first = true;
+  const uint8_t* p = nullptr;  // WIRE: the record's next byte, the bytes left in it, the bits held
+  int64_t left = 0;
+  uint64_t held = 0;
+  int fill = 0;
+  if constexpr (WIRE) {
+    p = w.wire + row * w.frame_bytes;
+    left = w.frame_bytes;
+  }
   for (int s = 0; s < a.S; ++s) {
-    const int64_t id = a.idx[int64_t(s) * a.rows + row];
+    int64_t id;
+    if constexpr (WIRE) {
+      while (fill < w.bits && left > 0) {  // never beyond the row's own bytes
+        held |= uint64_t(*p++) << fill;
+        fill += 8;
+        --left;
+      }
+      const uint32_t k = uint32_t(held) & ((1u << w.bits) - 1u);
+      held >>= w.bits;
+      fill -= w.bits;
+      id = k < uint32_t(w.K) ? int64_t(s) * w.K + k : -1;  // a field >= K is refused
+      if (w.idx_out && d0 == 0) w.idx_out[int64_t(s) * a.rows + row] = id;
+    } else {
+      id = a.idx[int64_t(s) * a.rows + row];
+    }
     if (id < 0 || id >= a.ncodes) continue;  // contributes zero; nothing is read through it
     const float* __restrict__ c = a.codebook + id * a.D + d0;
     float v[V];
@@ -311,59 +408,118 @@ __global__ __launch_bounds__(LK_T) void k_rvq_lookup_step(LookupArgs a, TO* __re
 using namespace sel;
 using namespace sel::vqstep;
 
-extern "C" {
+namespace {
 
-int sel_rvq_step(const float* z, int rows, int rows_per_sample, int D, const float* embeds, int S, int K,
-                 const int32_t* n_active, int flatten, int64_t* idx, float* zq, sel_stream_t stream) {
+// sel_rvq_step and sel_rvq_step_wire: one set of checks, one dispatch
+template <bool WIRE>
+int rvq_step_launch(const char* who, const float* z, int rows, int rows_per_sample, int D, const float* embeds, int S,
+                    int K, const int32_t* n_active, int flatten, int64_t* idx, float* zq, uint8_t* wire,
+                    sel_stream_t stream) {
   SEL_REQUIRE(rows >= 1 && rows_per_sample >= 1 && rows % rows_per_sample == 0, SEL_ERR_ARG,
-              "sel_rvq_step: rows (%d) must be a positive multiple of rows_per_sample (%d)", rows, rows_per_sample);
-  SEL_REQUIRE(D > 0 && D <= MAXD && K > 0 && S > 0, SEL_ERR_ARG, "sel_rvq_step: bad shape D=%d (1..%d) K=%d S=%d", D,
-              MAXD, K, S);
-  SEL_REQUIRE(z && embeds && idx, SEL_ERR_ARG, "sel_rvq_step: null z / embeds / idx");
-  SEL_REQUIRE(zq != z, SEL_ERR_ARG, "sel_rvq_step: zq aliases z");
+              "%s: rows (%d) must be a positive multiple of rows_per_sample (%d)", who, rows, rows_per_sample);
+  SEL_REQUIRE(D > 0 && D <= MAXD && K > 0 && S > 0, SEL_ERR_ARG, "%s: bad shape D=%d (1..%d) K=%d S=%d", who, D, MAXD,
+              K, S);
+  if constexpr (WIRE)
+    SEL_REQUIRE(z && embeds && wire, SEL_ERR_ARG, "%s: null z / embeds / wire", who);
+  else
+    SEL_REQUIRE(z && embeds && idx, SEL_ERR_ARG, "%s: null z / embeds / idx", who);
+  SEL_REQUIRE(zq != z, SEL_ERR_ARG, "%s: zq aliases z", who);
+  WireDst<WIRE> w;
+  if constexpr (WIRE) {
+    const int bits = wire_bits(K);
+    SEL_REQUIRE(bits <= 31 && (int64_t(1) << bits) >= K, SEL_ERR_ARG, "%s: K=%d needs more than 31 bits per field", who,
+                K);
+    SEL_REQUIRE(int64_t(S) * K <= (int64_t(1) << 40), SEL_ERR_ARG, "%s: S*K = %lld ids out of range", who,
+                (long long)(int64_t(S) * K));
+    w.wire = wire;
+    w.frame_bytes = (int64_t(S) * bits + 7) / 8;
+    w.bits = bits;
+  }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int cap = rows / rows_per_sample;
   if (D == COL_D && K == COL_K)
-    hipLaunchKernelGGL(k_rvq_step_col, dim3(unsigned(rows)), dim3(COL_T), 0, s, z, int64_t(rows), rows_per_sample,
-                       embeds, S, n_active, cap, flatten, idx, zq);
+    hipLaunchKernelGGL(k_rvq_step_col<WIRE>, dim3(unsigned(rows)), dim3(COL_T), 0, s, z, int64_t(rows),
+                       rows_per_sample, embeds, S, n_active, cap, flatten, idx, zq, w);
   else
-    hipLaunchKernelGGL(k_rvq_step_any, dim3(unsigned(rows)), dim3(ANY_T), 0, s, z, int64_t(rows), rows_per_sample, D,
-                       embeds, S, K, n_active, cap, flatten, idx, zq);
+    hipLaunchKernelGGL(k_rvq_step_any<WIRE>, dim3(unsigned(rows)), dim3(ANY_T), 0, s, z, int64_t(rows),
+                       rows_per_sample, D, embeds, S, K, n_active, cap, flatten, idx, zq, w);
   SEL_LAUNCH_CHECK();
   return SEL_OK;
 }
 
-int sel_rvq_lookup_step(const int64_t* idx, int rows, int rows_per_sample, int S, int64_t ncodes, int D,
-                        const float* codebook, const float* mean, const float* scale, const int32_t* n_active,
-                        int out_dtype, void* out, sel_stream_t stream) {
+// sel_rvq_lookup_step and sel_rvq_lookup_wire_step: idx, or the packed records of K-code stages
+template <bool WIRE>
+int rvq_lookup_launch(const char* who, const int64_t* idx, WireSrc<WIRE> w, int rows, int rows_per_sample, int S,
+                      int64_t ncodes, int D, const float* codebook, const float* mean, const float* scale,
+                      const int32_t* n_active, int out_dtype, void* out, sel_stream_t stream) {
   SEL_REQUIRE(rows >= 1 && rows_per_sample >= 1 && rows % rows_per_sample == 0, SEL_ERR_ARG,
-              "sel_rvq_lookup_step: rows (%d) must be a positive multiple of rows_per_sample (%d)", rows,
-              rows_per_sample);
-  SEL_REQUIRE(S > 0 && D > 0 && ncodes > 0, SEL_ERR_ARG, "sel_rvq_lookup_step: bad shape S=%d D=%d ncodes=%lld", S, D,
+              "%s: rows (%d) must be a positive multiple of rows_per_sample (%d)", who, rows, rows_per_sample);
+  SEL_REQUIRE(S > 0 && D > 0 && ncodes > 0, SEL_ERR_ARG, "%s: bad shape S=%d D=%d ncodes=%lld", who, S, D,
               (long long)ncodes);
-  SEL_REQUIRE(ncodes <= (int64_t(1) << 40) / D, SEL_ERR_ARG, "sel_rvq_lookup_step: codebook of %lld x %d out of range",
+  SEL_REQUIRE(ncodes <= (int64_t(1) << 40) / D, SEL_ERR_ARG, "%s: codebook of %lld x %d out of range", who,
               (long long)ncodes, D);
-  SEL_REQUIRE(idx && codebook && out, SEL_ERR_ARG, "sel_rvq_lookup_step: null idx / codebook / out");
-  SEL_REQUIRE((mean == nullptr) == (scale == nullptr), SEL_ERR_ARG,
-              "sel_rvq_lookup_step: mean and scale come together or not at all");
-  SEL_REQUIRE(out_dtype == SEL_F32 || out_dtype == SEL_BF16, SEL_ERR_ARG, "sel_rvq_lookup_step: out_dtype must be fp32 or bf16");
+  if constexpr (WIRE)
+    SEL_REQUIRE(w.wire && codebook && out, SEL_ERR_ARG, "%s: null wire / codebook / out", who);
+  else
+    SEL_REQUIRE(idx && codebook && out, SEL_ERR_ARG, "%s: null idx / codebook / out", who);
+  SEL_REQUIRE((mean == nullptr) == (scale == nullptr), SEL_ERR_ARG, "%s: mean and scale come together or not at all",
+              who);
+  SEL_REQUIRE(out_dtype == SEL_F32 || out_dtype == SEL_BF16, SEL_ERR_ARG, "%s: out_dtype must be fp32 or bf16", who);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
   const bool vec = D % 4 == 0 && al16(codebook) && al16(out) && al16(mean) && al16(scale);
   LookupArgs a{idx, codebook, mean, scale, n_active, int64_t(rows), ncodes, rows_per_sample, S, D,
                rows / rows_per_sample};
   const int64_t threads = int64_t(rows) * (vec ? D / 4 : D);
-  SEL_REQUIRE(threads / LK_T < (int64_t(1) << 31) - 1, SEL_ERR_ARG, "sel_rvq_lookup_step: rows * D out of range");
+  SEL_REQUIRE(threads / LK_T < (int64_t(1) << 31) - 1, SEL_ERR_ARG, "%s: rows * D out of range", who);
   const dim3 grid(unsigned((threads + LK_T - 1) / LK_T));
   if (out_dtype == SEL_F32) {
-    if (vec) hipLaunchKernelGGL((k_rvq_lookup_step<float, 4>), grid, dim3(LK_T), 0, s, a, static_cast<float*>(out));
-    else hipLaunchKernelGGL((k_rvq_lookup_step<float, 1>), grid, dim3(LK_T), 0, s, a, static_cast<float*>(out));
+    if (vec) hipLaunchKernelGGL((k_rvq_lookup_step<float, 4, WIRE>), grid, dim3(LK_T), 0, s, a, static_cast<float*>(out), w);
+    else hipLaunchKernelGGL((k_rvq_lookup_step<float, 1, WIRE>), grid, dim3(LK_T), 0, s, a, static_cast<float*>(out), w);
   } else {
-    if (vec) hipLaunchKernelGGL((k_rvq_lookup_step<__bf16, 4>), grid, dim3(LK_T), 0, s, a, static_cast<__bf16*>(out));
-    else hipLaunchKernelGGL((k_rvq_lookup_step<__bf16, 1>), grid, dim3(LK_T), 0, s, a, static_cast<__bf16*>(out));
+    if (vec) hipLaunchKernelGGL((k_rvq_lookup_step<__bf16, 4, WIRE>), grid, dim3(LK_T), 0, s, a, static_cast<__bf16*>(out), w);
+    else hipLaunchKernelGGL((k_rvq_lookup_step<__bf16, 1, WIRE>), grid, dim3(LK_T), 0, s, a, static_cast<__bf16*>(out), w);
   }
   SEL_LAUNCH_CHECK();
   return SEL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sel_rvq_step(const float* z, int rows, int rows_per_sample, int D, const float* embeds, int S, int K,
+                 const int32_t* n_active, int flatten, int64_t* idx, float* zq, sel_stream_t stream) {
+  return rvq_step_launch<false>("sel_rvq_step", z, rows, rows_per_sample, D, embeds, S, K, n_active, flatten, idx, zq,
+                                nullptr, stream);
+}
+
+int sel_rvq_step_wire(const float* z, int rows, int rows_per_sample, int D, const float* embeds, int S, int K,
+                      const int32_t* n_active, int flatten, int64_t* idx, float* zq, uint8_t* wire,
+                      sel_stream_t stream) {
+  return rvq_step_launch<true>("sel_rvq_step_wire", z, rows, rows_per_sample, D, embeds, S, K, n_active, flatten, idx,
+                               zq, wire, stream);
+}
+
+int sel_rvq_lookup_step(const int64_t* idx, int rows, int rows_per_sample, int S, int64_t ncodes, int D,
+                        const float* codebook, const float* mean, const float* scale, const int32_t* n_active,
+                        int out_dtype, void* out, sel_stream_t stream) {
+  return rvq_lookup_launch<false>("sel_rvq_lookup_step", idx, WireSrc<false>{}, rows, rows_per_sample, S, ncodes, D,
+                                  codebook, mean, scale, n_active, out_dtype, out, stream);
+}
+
+int sel_rvq_lookup_wire_step(const uint8_t* wire, int rows, int rows_per_sample, int S, int K, int D,
+                             const float* codebook, const float* mean, const float* scale, const int32_t* n_active,
+                             int out_dtype, void* out, int64_t* idx_out, sel_stream_t stream) {
+  const char* who = "sel_rvq_lookup_wire_step";
+  SEL_REQUIRE(S > 0 && K > 0, SEL_ERR_ARG, "%s: bad shape S=%d K=%d", who, S, K);
+  const int bits = wire_bits(K);
+  SEL_REQUIRE(bits <= 31 && (int64_t(1) << bits) >= K, SEL_ERR_ARG, "%s: K=%d needs more than 31 bits per field", who, K);
+  SEL_REQUIRE(int64_t(S) * K <= (int64_t(1) << 40), SEL_ERR_ARG, "%s: S*K = %lld ids out of range", who,
+              (long long)(int64_t(S) * K));
+  WireSrc<true> w{wire, idx_out, (int64_t(S) * bits + 7) / 8, K, bits};
+  return rvq_lookup_launch<true>(who, nullptr, w, rows, rows_per_sample, S, int64_t(S) * K, D, codebook, mean, scale,
+                                 n_active, out_dtype, out, stream);
 }
 
 }  // extern "C"

@@ -30,7 +30,9 @@ transmitter's hop and the codebook lookup in front of the receiver's, as
 stateless step launches (``sel_rvq_step`` / ``sel_rvq_lookup_step``,
 csrc/vq_step.hip) in second graphs beside the existing ones: ``transmit`` is
 then one replay from samples to code indices, ``receive`` one from code
-indices to samples.
+indices to samples.  ``enable_codes(wire=True)`` also puts the bytes of the
+wire format (sel/wire.py) inside the hop: ``transmit_packets`` is one replay from
+samples to packets, ``receive_packets`` one from packets to samples.
 """
 import functools
 
@@ -39,6 +41,7 @@ import torch
 from . import _lib as L
 from . import convops as CO
 from . import streamops as SO
+from .wire import WireFormat
 
 
 class _Half:
@@ -106,25 +109,36 @@ class _Half:
 
     # ---- code indices inside the hop (enable_codes) --------------------------------
     pre = post = codes_graph = idx = None
+    pre_wire = wire_graph = wire_buf = None
 
-    def add_codes(self, idx, pre=None, post=None):
+    def add_codes(self, idx, pre=None, post=None, wire_buf=None, pre_wire=None):
         """Extend the hop by a stateless launch in front of it (``pre``: the lookup
         into ``inp``) or behind it (``post``: the quantizer on ``outs[-1]``), as a
         second launch list beside ``launch`` -- and, for a captured half, a second
         graph beside ``graph``.  Only the new launch is warmed up eagerly (it has
-        no state); the capture itself executes nothing, so no carry moves."""
+        no state); the capture itself executes nothing, so no carry moves.
+        ``wire_buf``: the fixed (rows, frame_bytes) packet buffer -- ``post`` then
+        writes it beside ``idx``; ``pre_wire``, the lookup out of it, heads a third
+        launch list (and graph) beside ``pre``'s."""
         self.idx, self.pre, self.post = idx, pre, post
-        self.codes_graph = None
+        self.wire_buf, self.pre_wire = wire_buf, pre_wire
+        self.codes_graph = self.wire_graph = None
         if self.graph is not None:
             (pre or post)()
+            if pre_wire is not None:
+                pre_wire()
             torch.cuda.synchronize(self.inp.device)
             self.codes_graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.codes_graph):
-                self.launch_codes()
+                self.launch_codes(self.pre)
+            if pre_wire is not None:
+                self.wire_graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.wire_graph):
+                    self.launch_codes(self.pre_wire)
 
-    def launch_codes(self):
-        if self.pre is not None:
-            self.pre()
+    def launch_codes(self, pre):
+        if pre is not None:
+            pre()
         self.launch()
         if self.post is not None:
             self.post()
@@ -133,7 +147,15 @@ class _Half:
         if self.codes_graph is not None:
             self.codes_graph.replay()
         else:
-            self.launch_codes()
+            self.launch_codes(self.pre)
+        return self.outs[-1]
+
+    def run_wire(self):
+        """The receiver's hop from the packet buffer: lookup_wire_step -> steps -> commit."""
+        if self.wire_graph is not None:
+            self.wire_graph.replay()
+        else:
+            self.launch_codes(self.pre_wire)
         return self.outs[-1]
 
 
@@ -146,15 +168,24 @@ def _fill_idx(dst, idx, what):
     dst.copy_(idx.reshape(dst.shape))
 
 
+def _fill_packets(dst, p, what):
+    """p (n, packet_bytes) uint8 -> the fixed packet buffer (or its first n packets)."""
+    L.need_device(p)
+    if p.dtype != torch.uint8 or tuple(p.shape) != tuple(dst.shape):
+        raise L.SelError(f"sel: {what} takes uint8 packets of shape {tuple(dst.shape)}, got {p.dtype} {tuple(p.shape)}")
+    dst.copy_(p)
+
+
 class _CodesMixin:
     """``enable_codes`` / ``transmit`` / ``receive`` of sessions and pools: the
     quantizer behind the transmitter's hop and the codebook lookup in front of
     the receiver's, inside the hop's launch list (csrc/vq_step.hip)."""
     _tx = _rx = None          # the halves that carry codes once enable_codes ran
-    _codes_enabled = False
+    _codes_enabled = _wire_enabled = False
+    wire = None               # the WireFormat once enable_codes(wire=True) gave a half its packets
 
     @torch.no_grad()
-    def enable_codes(self, lookup_generator=None):
+    def enable_codes(self, lookup_generator=None, wire=False):
         """Put ``quantize`` behind ``encode`` and ``lookup`` in front of ``decode``:
         afterwards ``transmit`` is one replay from samples to code indices and
         ``receive`` one replay from code indices to samples.
@@ -168,10 +199,18 @@ class _CodesMixin:
         after the codebooks change.  With ``graph=True`` the extended hops are
         captured as NEW graphs beside the existing ones; ``encode`` / ``decode`` /
         ``quantize`` / ``lookup`` keep their graphs and their bits.  No carry and
-        no template row changes (safe after ``load_state()``)."""
+        no template row changes (safe after ``load_state()``).
+
+        ``wire=True`` adds the packets of the wire format (sel/wire.py; the layout
+        is ``self.wire``): the transmitter's quantizer launch writes them beside
+        the indices (``transmit`` keeps its bits, ``transmit_packets`` returns the
+        bytes of the same replay), and the receiver gets a third launch list and
+        graph that looks the codes up straight out of the packet buffer
+        (``receive_packets``), with no int64 buffer in between."""
         dev = self._dec.inp.device
         frames = self.plan.frames
-        self._tx = self._rx = None
+        self._tx = self._rx = self.wire = None
+        fmt = []
         enc = getattr(self, "_enc", None)
         if enc is not None and self.plan.pqc:
             rvq = self.generator.quantizer.codebook
@@ -183,7 +222,13 @@ class _CodesMixin:
             idx = torch.zeros((stack.shape[0], z.shape[0]), dtype=torch.int64, device=dev)
             count = getattr(enc, "n_active", None)
             self._prepare_codes(enc)
-            enc.add_codes(idx, post=functools.partial(SO.rvq_step, z, stack, idx, frames, count, True))
+            if wire:
+                fmt.append(WireFormat(stack.shape[0], stack.shape[2], frames))
+                buf = torch.zeros((z.shape[0], fmt[-1].frame_bytes), dtype=torch.uint8, device=dev)
+                enc.add_codes(idx, post=functools.partial(SO.rvq_step_wire, z, stack, buf, frames, count, True, idx),
+                              wire_buf=buf)
+            else:
+                enc.add_codes(idx, post=functools.partial(SO.rvq_step, z, stack, idx, frames, count, True))
             self._tx = enc
         lg = lookup_generator if lookup_generator is not None else self.lookup_generator
         dec = self._dec
@@ -203,9 +248,23 @@ class _CodesMixin:
                 scale = self.generator.scale.detach().to(dev, torch.float32).contiguous().clone()
             count = getattr(dec, "n_active", None)
             self._prepare_codes(dec)
-            dec.add_codes(idx, pre=functools.partial(SO.rvq_lookup_step, idx, flat, dec.inp, frames, mean, scale, count))
+            pre = functools.partial(SO.rvq_lookup_step, idx, flat, dec.inp, frames, mean, scale, count)
+            if wire:
+                if flat.shape[0] % S:
+                    raise L.SelError(f"sel: the lookup codebook's {flat.shape[0]} rows are not {S} stages of one size")
+                fmt.append(WireFormat(S, flat.shape[0] // S, frames))
+                buf = torch.zeros((idx.shape[1], fmt[-1].frame_bytes), dtype=torch.uint8, device=dev)
+                dec.add_codes(idx, pre=pre, wire_buf=buf,
+                              pre_wire=functools.partial(SO.rvq_lookup_wire_step, buf, flat, S, dec.inp, frames, mean,
+                                                         scale, count))
+            else:
+                dec.add_codes(idx, pre=pre)
             self._rx = dec
-        self._codes_enabled = True
+        if len(fmt) == 2 and (fmt[0].codebooks, fmt[0].codebook_size) != (fmt[1].codebooks, fmt[1].codebook_size):
+            raise L.SelError(f"sel: the transmitter packs {fmt[0]!r}, the lookup codebook reads {fmt[1]!r}")
+        if fmt:
+            self.wire = fmt[0]
+        self._codes_enabled, self._wire_enabled = True, bool(wire)
 
     def _prepare_codes(self, half):
         """Before a half's new launch is warmed up and captured (pools: no active stream)."""
@@ -213,13 +272,15 @@ class _CodesMixin:
     def _codes_half(self, which):
         if not self._codes_enabled:
             raise L.SelError(f"sel: {which} needs enable_codes() first")
-        if which == "transmit":
+        if which.endswith("_packets") and not self._wire_enabled:
+            raise L.SelError(f"sel: {which} needs enable_codes(wire=True) first")
+        if which.startswith("transmit"):
             if self._tx is None:
-                raise L.SelError("sel: transmit needs a transmitter with PQC: without it (or on a vocoder) encode's "
+                raise L.SelError(f"sel: {which} needs a transmitter with PQC: without it (or on a vocoder) encode's "
                                  "output is not the projector's fp32 code vector")
             return self._tx
         if self._rx is None:
-            raise L.SelError("sel: receive knows no lookup codebook: set lookup_generator (the generator whose "
+            raise L.SelError(f"sel: {which} knows no lookup codebook: set lookup_generator (the generator whose "
                              "codebooks decode the indices) and call enable_codes() again")
         return self._rx
 
@@ -333,6 +394,32 @@ class StreamSession(_CodesMixin):
         pl = self.plan
         _fill_idx(half.idx, idx, "session receive")
         return half.run_codes().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
+
+    # ---- the same in the bytes of the wire format (after enable_codes(wire=True)) -----
+    @torch.no_grad()
+    def transmit_packets(self, x):
+        """x (batch, in_channels, chunk) -> (batch, packet_bytes) uint8, ``self.wire``'s
+        packing of what ``transmit(x)`` returns: one replay (the one ``transmit``
+        runs).  A VIEW of a fixed buffer, valid until the next ``transmit`` /
+        ``transmit_packets``."""
+        half = self._codes_half("transmit_packets")
+        pl = self.plan
+        L.need_device(x)
+        if tuple(x.shape) != (pl.batch, pl.in_channels, pl.chunk):
+            raise L.SelError(f"sel: session transmit_packets takes {(pl.batch, pl.in_channels, pl.chunk)}, got "
+                             f"{tuple(x.shape)}")
+        half.inp.copy_(x.transpose(1, 2))
+        half.run_codes()
+        return half.wire_buf.view(pl.batch, self.wire.packet_bytes)
+
+    @torch.no_grad()
+    def receive_packets(self, p):
+        """p (batch, packet_bytes) uint8 -> y, what ``receive`` returns for the
+        indices in the packets: one replay, with no index tensor in between."""
+        half = self._codes_half("receive_packets")
+        pl = self.plan
+        _fill_packets(half.wire_buf.view(pl.batch, self.wire.packet_bytes), p, "session receive_packets")
+        return half.run_wire().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
 
     # ---- state ------------------------------------------------------------------
     def _layers(self):
@@ -477,6 +564,8 @@ class VocoderSession(_CodesMixin):
     # after enable_codes(): lookup, decode_norm and decode as one replay (transmit: always a SelError)
     transmit = StreamSession.transmit
     receive = StreamSession.receive
+    transmit_packets = StreamSession.transmit_packets
+    receive_packets = StreamSession.receive_packets
 
     # ---- state ------------------------------------------------------------------
     def _layers(self):
@@ -640,6 +729,35 @@ class _PoolBase(_CodesMixin):
         n = self._stage(half, slots)
         _fill_idx(half.idx[:, :n * pl.frames], idx, f"pool receive for {n} slots")
         out = half.run_codes()
+        return out.view(self.capacity, pl.out_samples, pl.out_channels)[:n].transpose(1, 2)
+
+    @torch.no_grad()
+    def transmit_packets(self, slots, x):
+        """x (n, in_channels, chunk) for the n listed slots -> (n, packet_bytes) uint8,
+        ``self.wire``'s packing of what ``transmit(slots, x)`` returns, packet i that
+        of ``slots[i]``: one replay.  A VIEW of a fixed buffer, valid until the next
+        ``transmit`` / ``transmit_packets``."""
+        half = self._codes_half("transmit_packets")
+        pl = self.plan
+        L.need_device(x)
+        if tuple(x.shape) != (len(slots), pl.in_channels, pl.chunk):
+            raise L.SelError(f"sel: pool transmit_packets takes {(len(slots), pl.in_channels, pl.chunk)} for "
+                             f"{len(slots)} slots, got {tuple(x.shape)}")
+        n = self._stage(half, slots)
+        half.inp[:n].copy_(x.transpose(1, 2))
+        half.run_codes()
+        return half.wire_buf.view(self.capacity, self.wire.packet_bytes)[:n]
+
+    @torch.no_grad()
+    def receive_packets(self, slots, p):
+        """p (n, packet_bytes) uint8, packet i for ``slots[i]`` -> y (n, out_channels,
+        samples), what ``receive`` returns for the indices in the packets: one replay."""
+        half = self._codes_half("receive_packets")
+        pl = self.plan
+        n = self._stage(half, slots)
+        _fill_packets(half.wire_buf.view(self.capacity, self.wire.packet_bytes)[:n], p,
+                      f"pool receive_packets for {n} slots")
+        out = half.run_wire()
         return out.view(self.capacity, pl.out_samples, pl.out_channels)[:n].transpose(1, 2)
 
     def _layers(self):

@@ -21,7 +21,9 @@ slot-indexed forms for stream pools (``sel.streaming.StreamPool``), and
 
 ``rvq_step`` / ``rvq_lookup_step`` bind the quantizer and the codebook lookup of a
 hop as stateless step launches (csrc/vq_step.hip), which
-``sel.streaming``'s ``enable_codes`` puts inside the hop's launch list.
+``sel.streaming``'s ``enable_codes`` puts inside the hop's launch list;
+``rvq_step_wire`` / ``rvq_lookup_wire_step`` are the same launches writing and
+reading the packed records of the wire format (``sel.wire``).
 """
 import ctypes
 from dataclasses import dataclass
@@ -285,6 +287,83 @@ def rvq_lookup_step(idx, codebook, out, rows_per_sample=1, mean=None, scale=None
     _count_operand("rvq_lookup_step", n_active)
     L.call("sel_rvq_lookup_step", L.ptr(idx), rows, rows_per_sample, S, ncodes, D, L.ptr(codebook), L.ptr(mean),
            L.ptr(scale), L.ptr(n_active), CO._code(out.dtype), L.ptr(out), L.stream())
+    return out
+
+
+# ---- the same with the wire format's records (include/sel.h, sel/wire.py) ----------------------
+def _wire_operand(what, wire, rows, S, K):
+    from .wire import WireFormat
+    fb = WireFormat(S, K).frame_bytes
+    if wire is None or wire.dtype != torch.uint8 or wire.dim() != 2 or tuple(wire.shape) != (rows, fb) \
+            or wire.stride() != (fb, 1):
+        raise L.SelError(f"sel: {what} takes a dense uint8 wire buffer of shape {(rows, fb)}, got "
+                         f"{None if wire is None else (wire.dtype, tuple(wire.shape), wire.stride())}")
+
+
+def rvq_step_wire(z, embeds, wire, rows_per_sample=1, n_active=None, flatten=True, idx=None, zq=None):
+    """One sel_rvq_step_wire launch on the current stream: rvq_step (same picks,
+    idx and zq, both optional here) that also writes every active row's packed
+    record into wire (rows, frame_bytes) uint8 -- dense rows, any byte alignment.
+    Nothing is allocated.  Returns wire."""
+    L.need_device(z, embeds, wire, idx, n_active, zq)
+    if embeds.dim() != 3 or embeds.dtype != torch.float32 or not embeds.is_contiguous():
+        raise L.SelError(f"sel: rvq_step_wire takes a contiguous fp32 (S, D, K) stack, got {embeds.dtype} "
+                         f"{tuple(embeds.shape)}")
+    S, D, K = embeds.shape
+    if z.dim() != 2 or z.shape[1] != D or z.dtype != torch.float32 or not z.is_contiguous():
+        raise L.SelError(f"sel: rvq_step_wire takes contiguous fp32 rows (rows, {D}), got {z.dtype} {tuple(z.shape)}")
+    rows = z.shape[0]
+    if idx is not None and (idx.dtype != torch.int64 or not idx.is_contiguous() or tuple(idx.shape) != (S, rows)):
+        raise L.SelError(f"sel: rvq_step_wire writes a contiguous int64 idx of shape {(S, rows)}, got {idx.dtype} "
+                         f"{tuple(idx.shape)}")
+    if zq is not None and (zq.dtype != torch.float32 or not zq.is_contiguous() or zq.shape != z.shape):
+        raise L.SelError(f"sel: rvq_step_wire writes a contiguous fp32 zq of shape {tuple(z.shape)}")
+    if rows_per_sample < 1 or rows % rows_per_sample:
+        raise L.SelError(f"sel: rvq_step_wire rows ({rows}) is not a multiple of rows_per_sample ({rows_per_sample})")
+    _wire_operand("rvq_step_wire", wire, rows, S, K)
+    _count_operand("rvq_step_wire", n_active)
+    L.call("sel_rvq_step_wire", L.ptr(z), rows, rows_per_sample, D, L.ptr(embeds), S, K, L.ptr(n_active),
+           int(bool(flatten)), L.ptr(idx), L.ptr(zq), L.ptr(wire), L.stream())
+    return wire
+
+
+def rvq_lookup_wire_step(wire, codebook, codebooks, out, rows_per_sample=1, mean=None, scale=None, n_active=None,
+                         idx_out=None):
+    """One sel_rvq_lookup_wire_step launch on the current stream: rvq_lookup_step
+    on the ids taken out of wire (rows, frame_bytes) uint8 -- dense rows, any byte
+    alignment -- for a codebook (codebooks * K, D) fp32.  A field >= K contributes
+    zero.  idx_out (codebooks, rows) int64, when given, receives the flattened
+    ids (-1 for such a field).  Nothing is allocated.  Returns out."""
+    L.need_device(wire, codebook, out, mean, scale, n_active, idx_out)
+    if codebook.dim() != 2 or codebook.dtype != torch.float32 or not codebook.is_contiguous():
+        raise L.SelError(f"sel: rvq_lookup_wire_step takes a contiguous fp32 (ncodes, D) codebook, got "
+                         f"{codebook.dtype} {tuple(codebook.shape)}")
+    ncodes, D = codebook.shape
+    S = int(codebooks)
+    if S < 1 or ncodes % S or ncodes < S:
+        raise L.SelError(f"sel: rvq_lookup_wire_step: a codebook of {ncodes} rows is not {S} stages of one size")
+    K = ncodes // S
+    if wire is None or wire.dim() != 2:
+        raise L.SelError("sel: rvq_lookup_wire_step takes a (rows, frame_bytes) uint8 wire buffer")
+    rows = wire.shape[0]
+    _wire_operand("rvq_lookup_wire_step", wire, rows, S, K)
+    if out.dtype not in (torch.float32, torch.bfloat16) or not out.is_contiguous() or out.numel() != rows * D:
+        raise L.SelError(f"sel: rvq_lookup_wire_step writes {rows} contiguous fp32 / bf16 rows of {D}, got {out.dtype} "
+                         f"{tuple(out.shape)}")
+    if idx_out is not None and (idx_out.dtype != torch.int64 or not idx_out.is_contiguous()
+                                or tuple(idx_out.shape) != (S, rows)):
+        raise L.SelError(f"sel: rvq_lookup_wire_step writes a contiguous int64 idx_out of shape {(S, rows)}")
+    if (mean is None) != (scale is None):
+        raise L.SelError("sel: rvq_lookup_wire_step takes mean and scale together or not at all")
+    for t in (mean, scale):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != D):
+            raise L.SelError(f"sel: rvq_lookup_wire_step takes contiguous fp32 mean / scale of {D} elements")
+    if rows_per_sample < 1 or rows % rows_per_sample:
+        raise L.SelError(f"sel: rvq_lookup_wire_step rows ({rows}) is not a multiple of rows_per_sample "
+                         f"({rows_per_sample})")
+    _count_operand("rvq_lookup_wire_step", n_active)
+    L.call("sel_rvq_lookup_wire_step", L.ptr(wire), rows, rows_per_sample, S, K, D, L.ptr(codebook), L.ptr(mean),
+           L.ptr(scale), L.ptr(n_active), CO._code(out.dtype), L.ptr(out), L.ptr(idx_out), L.stream())
     return out
 
 

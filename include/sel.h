@@ -424,6 +424,52 @@ int sel_rvq_lookup_step(const int64_t* idx, int rows, int rows_per_sample, int S
                         const float* codebook, const float* mean, const float* scale, const int32_t* n_active,
                         int out_dtype, void* out, sel_stream_t stream);
 
+/* ---- the wire format of the code indices, version 1 (csrc/vq_step.hip, sel/wire.py) ----
+ * What a transmitter sends per hop: the picks of sel_rvq_step, bit-packed.
+ *   bits        = max(1, ceil(log2 K)): the width of one field.
+ *   record      one per row: the S un-flattened codes k_s in [0, K), field s in bits
+ *               [s*bits, (s+1)*bits) of the record read as a little-endian bit
+ *               string -- bit i of the record is bit i % 8 of byte i / 8.
+ *   frame_bytes = ceil(S*bits / 8).  The pad bits of the last byte are written as
+ *               zero and ignored on reading.
+ *   packet      a stream's `frames` records of one hop back to back:
+ *               packet_bytes = frames * frame_bytes.  A wire buffer is a dense
+ *               (rows, frame_bytes) uint8 array in row order.
+ * Every row owns its bytes: no byte is shared between rows, so no two blocks write
+ * the same byte and nothing is atomic.  S = 8, K = 1024: 10 bytes per frame (at 160
+ * frames/s, 12.8 kbit/s).  There is no header, no sequence number and no checksum.
+ *
+ * Both calls below are single launches with the contract of their siblings above:
+ * no workspace, no allocation, no host synchronisation, capturable, the same
+ * active set (rows >= n * rows_per_sample: neither read nor written, wire bytes
+ * included), arguments validated before any device work (SEL_ERR_ARG).
+ *
+ * sel_rvq_step_wire: sel_rvq_step with the rows' records written by the same
+ * launch.  The picks, idx and zq are bit for bit sel_rvq_step's (one kernel body,
+ * instantiated with and without the record).  The first wave shifts each stage's
+ * pick into a 64-bit accumulator and stores the bytes that fill, so S stays
+ * unbounded; the last partial byte is stored zero-padded.  Byte stores only: wire
+ * may have any alignment.  idx may be NULL here (zq as before); wire must not be.
+ * Accepted: what sel_rvq_step accepts (idx apart), bits <= 31, S*K <= 2^40.
+ *
+ * sel_rvq_lookup_wire_step: sel_rvq_lookup_step on the ids s*K + k_s taken out of
+ * the records, with no int64 buffer in between; codebook is (S*K, D).  Same
+ * ascending round-to-nearest adds, same mean / scale step, same fp32 / bf16 store,
+ * same 16-byte path with an element-wise fallback (one kernel body again).
+ * Packets come off a network: a field >= K contributes zero and nothing is read
+ * through it; pad bits are ignored; wire is read byte by byte, never beyond a
+ * row's own frame_bytes, and may have any alignment.  idx_out (S, rows) int64,
+ * when non-null, receives the flattened ids, -1 for a refused field.
+ * Accepted: what sel_rvq_lookup_step accepts with ncodes = S*K (wire for idx),
+ * K > 0, bits <= 31, S*K <= 2^40. */
+#define SEL_WIRE_VERSION 1
+int sel_rvq_step_wire(const float* z, int rows, int rows_per_sample, int D, const float* embeds, int S, int K,
+                      const int32_t* n_active, int flatten, int64_t* idx, float* zq, uint8_t* wire,
+                      sel_stream_t stream);
+int sel_rvq_lookup_wire_step(const uint8_t* wire, int rows, int rows_per_sample, int S, int K, int D,
+                             const float* codebook, const float* mean, const float* scale, const int32_t* n_active,
+                             int out_dtype, void* out, int64_t* idx_out, sel_stream_t stream);
+
 /* ---- residual VQ, training mode: the EMA codebook update, vq_module.py:74-80 ----
  * Runs after sel_rvq_fwd on the same x / embeds / idx / counts.  Training mode
  * changes nothing about the assignment (every stage picks its code with its own

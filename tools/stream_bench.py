@@ -57,6 +57,18 @@ active, chunk 300, with the AudioDec decoder and the v1 vocoder on the receiver,
 and writes profiles/stream_codes_bench.{json,md} (the table of DESIGN §16).
 Acceptance: at B = 1 the transmitter's (b) must be faster than (a) by more than
 the wider 5-95 % band; every other row must be no slower by the same band.
+
+  python tools/stream_bench.py --wire
+measures what the packets of the wire format cost inside the hop
+(enable_codes(wire=True)), same protocol and objects as --codes, the old path
+being an enable_codes() object of the same kind:
+
+  transmit  against  transmit_packets      receive  against  receive_packets
+
+plus, recorded only, the transmitter's hop with the result brought to the host
+(transmit + idx.cpu() against transmit_packets + .cpu()), and writes
+profiles/stream_wire_bench.{json,md} (the table of DESIGN §17).  Acceptance:
+every *_packets row no slower than the row beside it by the wider 5-95 % band.
 """
 import argparse
 import json
@@ -471,6 +483,112 @@ def main_codes(a, dev):
     print("\n".join(lines + verdicts))
 
 
+def run_wire_config(kind, dtype, N, chunk, hops, warmup, dev):
+    """transmit / transmit_packets and receive / receive_packets (AudioDec decoder
+    and v1 vocoder), `kind` = "session" (batch N) or "pool" (N of N slots
+    active), at full width, old and new on separate objects as run_codes_config;
+    tx_host is the transmitter's hop with its result copied to the host."""
+    from models.autoencoder.AudioDec import StreamGenerator as Encoder
+    from models.vocoder.HiFiGAN import StreamGenerator as Vocoder
+    from sel import configs
+    from sel.streaming import StreamPool, StreamSession, VocoderPool, VocoderSession
+    torch.manual_seed(93)
+    E = Encoder().to(dev).eval()
+    E.quantizer.initial()
+    V = Vocoder(**configs.VOCODER_V1).to(dev).eval()
+    L = chunk // 300
+    x = 0.1 * torch.randn(N, 1, chunk, generator=torch.Generator().manual_seed(1)).to(dev)
+    idx = E.quantize(E.encode(x))
+    pool = kind == "pool"
+    idx = idx.view(idx.shape[0], N, L)
+    if not pool and N == 1:
+        idx = idx.squeeze(1)
+
+    def make_ae():
+        return StreamPool(E, N, chunk, graph=True, dtype=dtype) if pool else StreamSession(E, N, chunk, graph=True,
+                                                                                           dtype=dtype)
+
+    def make_v1():
+        return VocoderPool(V, N, L, graph=True, dtype=dtype) if pool else VocoderSession(V, N, L, graph=True,
+                                                                                         dtype=dtype)
+
+    objs = {}
+    for name, make in (("ae", make_ae), ("v1", make_v1)):
+        old, new, old_h, new_h = make(), make(), make(), make()
+        for o, wire in ((old, False), (new, True), (old_h, False), (new_h, True)):
+            o.lookup_generator = E
+            o.enable_codes(wire=wire)
+        objs[name] = (old, new, old_h, new_h)
+    sl = ()
+    if pool:
+        for group in objs.values():
+            for o in group:
+                sl = ([o.open() for _ in range(N)],)
+    ae_old, ae_new, ae_old_h, ae_new_h = objs["ae"]
+    v1_old, v1_new = objs["v1"][:2]
+    packets = ae_new.wire.pack(idx.cpu()).to(dev)
+    paths = {"tx": (lambda: ae_old.transmit(*sl, x), lambda: ae_new.transmit_packets(*sl, x)),
+             "rx": (lambda: ae_old.receive(*sl, idx), lambda: ae_new.receive_packets(*sl, packets)),
+             "rx_v1": (lambda: v1_old.receive(*sl, idx), lambda: v1_new.receive_packets(*sl, packets)),
+             "tx_host": (lambda: ae_old_h.transmit(*sl, x).cpu(), lambda: ae_new_h.transmit_packets(*sl, x).cpu())}
+    stream = torch.cuda.current_stream(dev)
+    rec = {h: {p: dict(host=[], gpu=[]) for p in ("old", "new")} for h in paths}
+    for hop in range(warmup + hops):
+        for half, fns in paths.items():
+            for p, fn in zip(("old", "new"), fns):
+                _, h, g = _timed(fn, stream)
+                if hop >= warmup:
+                    rec[half][p]["host"].append(h)
+                    rec[half][p]["gpu"].append(g)
+    w = ae_new.wire
+    return dict(kind=kind, dtype=str(dtype).replace("torch.", ""), streams=N, chunk=chunk, hops=hops,
+                wire=dict(version=w.version, bits=w.bits, frame_bytes=w.frame_bytes, packet_bytes=w.packet_bytes,
+                          index_bytes=8 * w.codebooks * w.frames),
+                halves={h: {p: {k: _stats(v) for k, v in r.items()} for p, r in d.items()} for h, d in rec.items()})
+
+
+def main_wire(a, dev):
+    results = []
+    for dt in a.dtypes:
+        for kind, N in (("session", 1), ("session", a.streams), ("pool", a.streams)):
+            r = run_wire_config(kind, getattr(torch, dt), N, 300, a.hops, a.warmup, dev)
+            results.append(r)
+            print(json.dumps(r), flush=True)
+    label = {("tx", "old"): "transmit", ("tx", "new"): "transmit_packets",
+             ("rx", "old"): "receive", ("rx", "new"): "receive_packets",
+             ("rx_v1", "old"): "v1 receive", ("rx_v1", "new"): "v1 receive_packets",
+             ("tx_host", "old"): "transmit + idx.cpu() (recorded only)",
+             ("tx_host", "new"): "transmit_packets + .cpu() (recorded only)"}
+    lines = ["| dtype | object | half | path | host ms med (p5-p95) | GPU ms med (p5-p95) |", "|---|---|---|---|---|---|"]
+    verdicts = []
+    for r in results:
+        what = f"{r['kind']} B={r['streams']}" if r["kind"] == "session" else f"pool {r['streams']} of {r['streams']}"
+        for half, d in r["halves"].items():
+            for p in ("old", "new"):
+                h, g = d[p]["host"], d[p]["gpu"]
+                lines.append(f"| {r['dtype']} | {what} | {half} | {label[half, p]} | "
+                             f"{h['med']:.3f} ({h['p5']:.3f}-{h['p95']:.3f}) | "
+                             f"{g['med']:.3f} ({g['p5']:.3f}-{g['p95']:.3f}) |")
+            if half == "tx_host":
+                continue
+            o, n = d["old"]["host"], d["new"]["host"]
+            gain = o["med"] - n["med"]
+            spread = max(o["p95"] - o["p5"], n["p95"] - n["p5"])
+            verdicts.append(f"acceptance {r['dtype']} {what} {half} (no slower): old {o['med']:.3f} ms - new "
+                            f"{n['med']:.3f} ms = {gain:.3f} ms vs 5-95% band {spread:.3f} ms: "
+                            f"{'MET' if gain >= -spread else 'NOT MET'}")
+    w = results[0]["wire"]
+    verdicts.append(f"wire v{w['version']}: {w['bits']} bits per field, {w['frame_bytes']} bytes per frame against "
+                    f"{w['index_bytes']} bytes of int64 indices")
+    out = a.out or os.path.join(REPO, "profiles", "stream_wire_bench")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out + ".json", "w") as f:
+        json.dump(results, f, indent=1)
+    with open(out + ".md", "w") as f:
+        f.write("\n".join(lines + [""] + verdicts) + "\n")
+    print("\n".join(lines + verdicts))
+
+
 def main_vocoder(a, dev):
     results = []
     for dec in a.decoder:
@@ -527,6 +645,9 @@ def main():
     ap.add_argument("--codes", action="store_true",
                     help="quantize / lookup inside the hop graphs: encode + quantize against transmit, lookup + "
                          "decode against receive (profiles/stream_codes_bench)")
+    ap.add_argument("--wire", action="store_true",
+                    help="the packets of the wire format inside the hop graphs: transmit against transmit_packets, "
+                         "receive against receive_packets (profiles/stream_wire_bench)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -536,6 +657,8 @@ def main():
         sys.exit("stream_bench: --attribution goes with --pool")
     if a.codes:
         return main_codes(a, dev)
+    if a.wire:
+        return main_wire(a, dev)
     if a.pool:
         return main_attribution(a, dev) if a.attribution else main_pool(a, dev)
     if a.decoder != ["audiodec"]:
