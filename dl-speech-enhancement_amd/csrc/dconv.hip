@@ -774,7 +774,24 @@ __global__ __launch_bounds__(256) void k_dconv_shortx(D d, const T* __restrict__
 // of gout[b, j, col(g, o)] * x[b, j + q0 + i, r*Cs + g*Cg + c]; bias partials
 // gb[col] = sum gout.  part[split][...] (fp32), reduced by k_dwgrad_finish.
 // ---------------------------------------------------------------------------
-// VALU: thread per weight element, rows of its split.
+// VALU: thread per weight element, rows of its split.  A split can be every
+// row of the layer (wg_plan: one split when the layer has >= 2^20 weights), so
+// the fp32 kernel sums its rows with compensation (Kahan): a plain running fp32
+// sum of 16400 full-mantissa terms was 2e-6 off norm-wise, 20 x a pairwise
+// sum's error (tests/test_gpu_dconv_edges.py).  bf16 products carry 16
+// mantissa bits and lose an order of magnitude less: plain sum there.
+template <typename T>
+__device__ __forceinline__ void dwgrad_add(float& acc, float& comp, float g, float xv) {
+  if constexpr (sizeof(T) == 4) {
+    const float y = fmaf(g, xv, -comp);
+    const float t = acc + y;
+    comp = (t - acc) - y;
+    acc = t;
+  } else {
+    acc += g * xv;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_dwgrad_valu(D d, const T* __restrict__ gout, const T* __restrict__ x,
                                                      int rows_per_split, float* __restrict__ part,
@@ -787,7 +804,7 @@ __global__ __launch_bounds__(256) void k_dwgrad_valu(D d, const T* __restrict__ 
   const int64_t r0 = int64_t(blockIdx.y) * rows_per_split;
   const int64_t r1 = r0 + rows_per_split < total_rows ? r0 + rows_per_split : total_rows;
   for (int64_t idx = int64_t(blockIdx.x) * 256 + threadIdx.x; idx < nw + nb; idx += int64_t(gridDim.x) * 256) {
-    float acc = 0.f;
+    float acc = 0.f, comp = 0.f;
     if (idx < nw) {
       const int rc = int(idx % nred);
       const int i = int((idx / nred) % d.K);
@@ -799,7 +816,8 @@ __global__ __launch_bounds__(256) void k_dwgrad_valu(D d, const T* __restrict__ 
       for (int64_t rr = r0; rr < r1; ++rr) {
         const int t = j + d.q0 + i;
         if (t >= 0 && t < d.Tv)
-          acc += to_f(gout[(int64_t(b) * d.Tvo + j) * d.ldo + oc]) * to_f(x[(int64_t(b) * d.Tvs + t) * d.ldx + ic]);
+          dwgrad_add<T>(acc, comp, to_f(gout[(int64_t(b) * d.Tvo + j) * d.ldo + oc]),
+                        to_f(x[(int64_t(b) * d.Tvs + t) * d.ldx + ic]));
         if (++j == d.Tvalid) j = 0, ++b;
       }
       part[int64_t(blockIdx.y) * nw + idx] = acc;
@@ -809,7 +827,7 @@ __global__ __launch_bounds__(256) void k_dwgrad_valu(D d, const T* __restrict__ 
       const int64_t oc = out_col(d, g, o);
       int b = int(r0 / d.Tvalid), j = int(r0 - int64_t(b) * d.Tvalid);
       for (int64_t rr = r0; rr < r1; ++rr) {
-        acc += to_f(gout[(int64_t(b) * d.Tvo + j) * d.ldo + oc]);
+        dwgrad_add<T>(acc, comp, to_f(gout[(int64_t(b) * d.Tvo + j) * d.ldo + oc]), 1.f);
         if (++j == d.Tvalid) j = 0, ++b;
       }
       bpart[int64_t(blockIdx.y) * nb + go] = acc;
@@ -2183,7 +2201,7 @@ int dispatch_fwd(const sel_dconv_desc* d, const void* x, const void* wp, const f
 
 struct WgPlanD {
   int flat_p;  // k_dwgrad_w3 flat tiling pitch (0: per-sequence tiles)
-  bool mfma, shortk, w3;
+  bool mfma, shortk, shortx, w3;  // shortx: the short reduction on the staged kernel (k_dwgrad_shortx)
   int w3_nt, w3_ct, w3_maxt;
   int nsplit, bsplit;
   int rows_per_split, brows_per_split;
@@ -2193,6 +2211,27 @@ struct WgPlanD {
 // split-partial budget per layer (bytes; tune key 45 > 0: MB, A/B sweeps)
 inline int64_t wg_cap() { return int64_t(tune(45) > 0 ? tune(45) : 64) << 20; }
 
+// the staged short weight-gradient kernel's (K, NR) instances
+#define SEL_DWSX_TABLE(X) X(15, 1) X(2, 3) X(3, 1) X(2, 1) X(6, 1) X(1, 2) X(1, 3)
+bool dwshortx_inst(int K, int nred) {
+#define SEL_DWSX_HAS(K_, NR_) if (K == K_ && nred == NR_) return true;
+  SEL_DWSX_TABLE(SEL_DWSX_HAS)
+#undef SEL_DWSX_HAS
+  return false;
+}
+
+// the k_dwgrad_w3<NT, CT, MAXT> instances wg_plan can ask for: (nt, ct) in
+// {1, 2}^2 and K = 1..8 give exactly these 16 (MAXT = per-wave pair count
+// ceil(CT K / (waves per pair set)), 6..8 rounded up to the 8-slot form);
+// tests/test_dconv_cases_host.py holds this list to that enumeration
+#define SEL_W3_TABLE(X)                                   \
+  X(1, 1, 1) X(1, 1, 2)                                   \
+  X(1, 2, 1) X(1, 2, 2) X(1, 2, 3) X(1, 2, 4)             \
+  X(2, 1, 1) X(2, 1, 2) X(2, 1, 3) X(2, 1, 4)             \
+  X(2, 2, 1) X(2, 2, 2) X(2, 2, 3) X(2, 2, 4) X(2, 2, 5) X(2, 2, 8)
+
+// Which weight-gradient kernel a layer takes and how its rows are split: the
+// single decision the launcher (wgrad_fill) and sel_dconv_wgrad_kernel use.
 WgPlanD wg_plan(const sel_dconv_desc* d, int dtype) {
   WgPlanD p{};
   const int width = d->So * d->Ng;
@@ -2208,6 +2247,9 @@ WgPlanD wg_plan(const sel_dconv_desc* d, int dtype) {
     p.rows_per_split = int((rows + want - 1) / want);
     p.nsplit = int((rows + p.rows_per_split - 1) / p.rows_per_split);
     p.bsplit = p.nsplit;
+    // staged kernel (tune key 18: 1 = off) where the phase view is contiguous
+    p.shortx = tune(18) != 1 && d->Cs == d->Cg && d->ldx == nred && d->Ng % 2 == 0 && d->ldo % 2 == 0 &&
+               int64_t(d->B) * d->Tvo < (int64_t(1) << 31) && dwshortx_inst(d->K, nred);
     return p;
   }
   p.w3 = p.mfma && d->G == 1 && d->So == 1 && (d->S == 1 || d->Cs == d->Cg) && d->K <= 8 && width % 32 == 0 &&
@@ -2265,6 +2307,9 @@ WgPlanD wg_plan(const sel_dconv_desc* d, int dtype) {
   return p;
 }
 
+// bias partials the final reduction reads (the VALU kernel writes one per row split)
+inline int wg_bsplit(const WgPlanD& p) { return (p.mfma || p.shortk) ? p.bsplit : p.nsplit; }
+
 size_t wg_bytes(const sel_dconv_desc* d, const WgPlanD& p) {
   const int64_t width = int64_t(d->So) * d->Ng;
   const int64_t nw = int64_t(d->G) * width * d->K * d->S * d->Cg;
@@ -2280,9 +2325,7 @@ hipError_t wgrad_fill(const sel_dconv_desc* d, int dtype, const WgPlanD& p, cons
   const int nred = d->S * d->Cg;
   if (p.shortk) {
     const int kr = d->K * nred;
-    // staged kernel (tune key 18: 1 = off) where the phase view is contiguous
-    if (tune(18) != 1 && d->Cs == d->Cg && d->ldx == nred && d->Ng % 2 == 0 && d->ldo % 2 == 0 &&
-        int64_t(d->B) * d->Tvo < (int64_t(1) << 31)) {
+    if (p.shortx) {
       const int rl = 256 / (d->Ng / 2), rb = rl * 16;
       const size_t lds = std::max<size_t>(size_t(rb + d->K - 1) * nred, size_t(rl) * d->Ng * (kr + 1)) * sizeof(float);
       void (*kx)(D, const __bf16*, const __bf16*, float*, float*) = nullptr;
@@ -2292,22 +2335,21 @@ hipError_t wgrad_fill(const sel_dconv_desc* d, int dtype, const WgPlanD& p, cons
     kx = k_dwgrad_shortx<__bf16, K_, NR_>;                                      \
     kf = k_dwgrad_shortx<float, K_, NR_>;                                       \
   }
-      SEL_DWSX(15, 1) SEL_DWSX(2, 3) SEL_DWSX(3, 1) SEL_DWSX(2, 1) SEL_DWSX(6, 1) SEL_DWSX(1, 2) SEL_DWSX(1, 3)
+      SEL_DWSX_TABLE(SEL_DWSX)
 #undef SEL_DWSX
-      if (kx) {
-        const void* kern = dtype == SEL_BF16 ? (const void*)kx : (const void*)kf;
-        if (lds > 64 * 1024) {
-          const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
-          if (e != hipSuccess) return e;
-        }
-        if (dtype == SEL_BF16)
-          hipLaunchKernelGGL(kx, dim3(p.nsplit), dim3(256), lds, s, *d, static_cast<const __bf16*>(gout),
-                             static_cast<const __bf16*>(x), part, bpart);
-        else
-          hipLaunchKernelGGL(kf, dim3(p.nsplit), dim3(256), lds, s, *d, static_cast<const float*>(gout),
-                             static_cast<const float*>(x), part, bpart);
-        return hipGetLastError();
+      if (!kx) return hipErrorInvalidValue;
+      const void* kern = dtype == SEL_BF16 ? (const void*)kx : (const void*)kf;
+      if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, int(lds));
+        if (e != hipSuccess) return e;
       }
+      if (dtype == SEL_BF16)
+        hipLaunchKernelGGL(kx, dim3(p.nsplit), dim3(256), lds, s, *d, static_cast<const __bf16*>(gout),
+                           static_cast<const __bf16*>(x), part, bpart);
+      else
+        hipLaunchKernelGGL(kf, dim3(p.nsplit), dim3(256), lds, s, *d, static_cast<const float*>(gout),
+                           static_cast<const float*>(x), part, bpart);
+      return hipGetLastError();
     }
 #define SEL_DWS(TT, KR)                                                                                     \
   hipLaunchKernelGGL((k_dwgrad_short<TT, KR>), dim3(p.nsplit), dim3(256), 0, s, *d, static_cast<const TT*>(gout), \
@@ -2325,10 +2367,7 @@ hipError_t wgrad_fill(const sel_dconv_desc* d, int dtype, const WgPlanD& p, cons
     const int64_t ntiles = p.flat_p ? p.tiles_per_seq : int64_t(d->B) * p.tiles_per_seq;
     dim3 grid(unsigned(p.nsplit), unsigned(width / NB), unsigned(nred / CB));
 #define SEL_W3(NT_, CT_, MT_)                                                                                    if (p.w3_nt == NT_ && p.w3_ct == CT_ && p.w3_maxt == MT_) {                                                      auto kern = k_dwgrad_w3<NT_, CT_, MT_>;                                                                        if (lds > 64 * 1024) {                                                                                           const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,                                                int(lds));                                                            if (e != hipSuccess) return e;                                                                               }                                                                                                              hipLaunchKernelGGL(kern, grid, dim3(256), lds, s, *d, static_cast<const __bf16*>(gout),                                            static_cast<const __bf16*>(x), p.tiles_per_seq, ntiles, p.tiles_per_split, part, p.flat_p, bpart);  } else
-    SEL_W3(1, 1, 1) SEL_W3(1, 1, 2) SEL_W3(1, 1, 3) SEL_W3(1, 1, 4) SEL_W3(1, 1, 5)
-    SEL_W3(1, 2, 1) SEL_W3(1, 2, 2) SEL_W3(1, 2, 3) SEL_W3(1, 2, 4) SEL_W3(1, 2, 5)
-    SEL_W3(2, 1, 1) SEL_W3(2, 1, 2) SEL_W3(2, 1, 3) SEL_W3(2, 1, 4) SEL_W3(2, 1, 5) SEL_W3(2, 1, 8)
-    SEL_W3(2, 2, 1) SEL_W3(2, 2, 2) SEL_W3(2, 2, 3) SEL_W3(2, 2, 4) SEL_W3(2, 2, 5) SEL_W3(2, 2, 8)
+    SEL_W3_TABLE(SEL_W3)
     { return hipErrorInvalidValue; }
 #undef SEL_W3
     return hipGetLastError();  // (bias partials: in the kernel, p.bsplit == p.nsplit)
@@ -2410,6 +2449,39 @@ int sel_dconv_kernel(const sel_dconv_desc* d, int dtype, char* name, size_t cap)
   return p.path;
 }
 
+int sel_dconv_wgrad_kernel(const sel_dconv_desc* d, int dtype, char* name, size_t cap, int32_t plan[4]) {
+  if (!d || check(d) != SEL_OK || (dtype != SEL_BF16 && dtype != SEL_F32) || d->So != 1) return -1;
+  const WgPlanD p = wg_plan(d, dtype);
+  const int nred = d->S * d->Cg;
+  if (name && cap) {
+    const char* t = dtype == SEL_BF16 ? "bf16" : "float";
+    if (p.shortk && p.shortx) snprintf(name, cap, "k_dwgrad_shortx<%s, %d, %d>", t, d->K, nred);
+    else if (p.shortk) snprintf(name, cap, "k_dwgrad_short<%s, %d>", t, d->K * nred);
+    else if (p.w3) snprintf(name, cap, "k_dwgrad_w3<%d, %d, %d>", p.w3_nt, p.w3_ct, p.w3_maxt);
+    else if (p.mfma) snprintf(name, cap, "k_dwgrad_mfma<%d>", p.nt);
+    else snprintf(name, cap, "k_dwgrad_valu<%s>", t);
+  }
+  if (plan) {
+    plan[0] = p.nsplit;
+    plan[1] = (p.w3 || p.mfma) ? p.tiles_per_split : p.rows_per_split;
+    plan[2] = wg_bsplit(p);
+    plan[3] = p.flat_p;
+  }
+  return SEL_OK;
+}
+
+int sel_dconv_w3_instances(int32_t* triples, int cap) {
+  static const int32_t tab[][3] = {
+#define SEL_W3_ROW(NT_, CT_, MT_) {NT_, CT_, MT_},
+      SEL_W3_TABLE(SEL_W3_ROW)
+#undef SEL_W3_ROW
+  };
+  const int n = int(sizeof(tab) / sizeof(tab[0]));
+  for (int i = 0; triples && i < n && i < cap; ++i)
+    for (int e = 0; e < 3; ++e) triples[3 * i + e] = tab[i][e];
+  return n;
+}
+
 size_t sel_dconv_wgrad_workspace(const sel_dconv_desc* d, int dtype) {
   if (!d || check(d) != SEL_OK) return 16;
   return wg_bytes(d, wg_plan(d, dtype));
@@ -2485,7 +2557,7 @@ int sel_dconv_wgrad_partials(const sel_dconv_desc* d, int dtype, const void* gou
   const int64_t nw = int64_t(N) * d->K * d->S * d->Cg;
   float* bpart = gb ? part + int64_t(p.nsplit) * nw : nullptr;
   SEL_HIP(wgrad_fill(d, dtype, p, gout, x, part, bpart, s));
-  const int bsplit = (p.mfma || p.shortk) ? p.bsplit : p.nsplit;
+  const int bsplit = wg_bsplit(p);
   int nsplit = p.nsplit;
   if (nsplit > PRESUM) {  // fold the partials to <= PRESUM per weight before the per-output pass
     float* tmp = part + int64_t(p.nsplit) * nw + int64_t(std::max(p.bsplit, p.nsplit)) * N;

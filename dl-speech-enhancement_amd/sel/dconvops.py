@@ -247,6 +247,25 @@ def kernel(desc, dtype):
     return PATH_NAMES[path], buf.value.decode()
 
 
+def wgrad_kernel(desc, dtype):
+    """(kernel name, (nsplit, tiles or rows per split, bias splits, flat pitch))
+    of the weight gradient of a forward layer descriptor (include/sel.h
+    sel_dconv_wgrad_kernel; the launcher's own decision, no GPU needed)."""
+    buf = ctypes.create_string_buffer(96)
+    plan = (ctypes.c_int32 * 4)()
+    if L.load().sel_dconv_wgrad_kernel(ctypes.byref(desc), _code(dtype), buf, 96, plan) != 0:
+        raise L.SelError(f"sel_dconv_wgrad_kernel: invalid descriptor: {L.load().sel_last_error().decode()}")
+    return buf.value.decode(), tuple(plan)
+
+
+def w3_instances():
+    """The (NT, CT, MAXT) instances of k_dwgrad_w3 in the library."""
+    n = L.load().sel_dconv_w3_instances(None, 0)
+    tab = (ctypes.c_int32 * (3 * n))()
+    L.load().sel_dconv_w3_instances(tab, n)
+    return [tuple(tab[3 * i:3 * i + 3]) for i in range(n)]
+
+
 def _meta(d, x, out, tag):
     """(kernel name, algorithmic bytes, flops) of one launch for the bench
     timer: launches are classified by the kernel they run (the name rocprofv3

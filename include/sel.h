@@ -722,6 +722,17 @@ size_t sel_dconv_wgrad_workspace(const sel_dconv_desc* d, int dtype);
 int sel_dconv_wgrad(const sel_dconv_desc* d, int dtype, const void* gout, const void* x, int N, int Cg, int Kt,
                     int stride, int pad, const float* v, const float* wg, float* gw, float* gg, float* gb, void* ws,
                     size_t ws_bytes, sel_stream_t stream);
+/* The weight-gradient kernel a forward layer descriptor (So = 1) takes and how
+ * its rows are split (the launcher's own decision, current tune knobs included;
+ * no GPU needed): the kernel's name as rocprofv3 lists it into name[cap] when
+ * name != NULL, and plan = {nsplit, 128- or 64-row tiles (k_dwgrad_w3 /
+ * k_dwgrad_mfma) or rows (the others) per split, bias partials the final
+ * reduction reads, row pitch of k_dwgrad_w3's flat tiling (0: per-sequence
+ * tiles)} when plan != NULL.  Returns -1 for an invalid descriptor. */
+int sel_dconv_wgrad_kernel(const sel_dconv_desc* d, int dtype, char* name, size_t cap, int32_t plan[4]);
+/* The (NT, CT, MAXT) instances of k_dwgrad_w3 the library holds, 3 ints each
+ * into triples[3 * cap] (NULL: count only); returns their number. */
+int sel_dconv_w3_instances(int32_t* triples, int cap);
 /* sel_dconv_wgrad in two phases, so that several layers' final reductions run
  * as one launch: _partials writes the split partials into ws (which must stay
  * allocated, in stream order, until the finish) and describes the reduction

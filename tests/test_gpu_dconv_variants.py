@@ -141,8 +141,10 @@ def test_ws_tiles_match_fp64_and_pf(gpu, shape):
     (dconv_ws_fwd; tune key 21 = 1 keeps them on k_dconv_pf): forward with
     bias + LeakyReLU and 3 zero rows past the computed ones, adjoint with the
     (+ res) * LeakyReLU'(aux) epilogue, both against fp64 torch of the same bf16
-    operands (bound 1e-2 norm-wise: output rounding only) and against the pf
-    kernel (another fp32 summation order: <= 5e-3)."""
+    operands (output rounding only: 4e-3 norm-wise and 8e-3 |ref| + 2e-3 max |ref|
+    per element, dconv_cases.check_bf16) and against the pf kernel (another fp32
+    summation order: <= 5e-3)."""
+    from dconv_cases import check_bf16
     from sel import _lib as Lb
     from sel import dconvops as DC
     lib = Lb.lib()
@@ -190,8 +192,8 @@ def test_ws_tiles_match_fp64_and_pf(gpu, shape):
         lib.sel_tune(21, prev)
     assert torch.count_nonzero(y[:, T_out:]).item() == 0
     rel = lambda a, r: ((a.double() - r).norm() / r.norm()).item()  # noqa: E731
-    assert rel(y[:, :T_out], ref_y) <= 1e-2, (tag, "fwd", rel(y[:, :T_out], ref_y))
-    assert rel(gin[:, :T], ref_gin) <= 1e-2, (tag, "adjoint", rel(gin[:, :T], ref_gin))
+    check_bf16(y[:, :T_out], ref_y, f"{tag} fwd")
+    check_bf16(gin[:, :T], ref_gin, f"{tag} adjoint")
     assert rel(y, y_pf.double()) <= 5e-3, (tag, "fwd vs pf", rel(y, y_pf.double()))
     assert rel(gin, gin_pf.double()) <= 5e-3, (tag, "adjoint vs pf", rel(gin, gin_pf.double()))
 

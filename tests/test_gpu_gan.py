@@ -142,7 +142,10 @@ def test_dconv_layer_fwd_dgrad_wgrad(gpu, shape, dtype):
     """One discriminator layer through the primitive (forward, adjoint, weight /
     bias gradient) against fp64 torch on the same operands, MFMA and VALU
     kernels both (tune key 9 = 1 forces the VALU kernel).  Bounds: fp32 1e-5
-    (fwd) / 1e-4 (grads); bf16: operand rounding only, 1e-2 / 2e-2."""
+    (fwd) / 1e-4 (grads); bf16 forward and adjoint: one rounded output of fp32
+    sums of exact products, 4e-3 norm-wise and 8e-3 |ref| + 2e-3 max |ref| per
+    element (dconv_cases.check_bf16); bf16 weight / bias gradients 2e-2."""
+    from dconv_cases import check_bf16
     from sel import _lib as Lb
     from sel import dconvops as DC
     tag, cin, cout, Kt, s, pad, G, Bs, T = shape
@@ -165,7 +168,7 @@ def test_dconv_layer_fwd_dgrad_wgrad(gpu, shape, dtype):
     br = b.double().clone().requires_grad_(True)
     pre = torch.nn.functional.conv1d(xr.permute(0, 2, 1), wr, br, stride=s, padding=pad, groups=G).permute(0, 2, 1)
     pre.backward(gy.to(dt).double())
-    tf, tg = (1e-5, 1e-4) if dtype == "fp32" else (1e-2, 2e-2)
+    tf, tg = (1e-5, 1e-4) if dtype == "fp32" else (4e-3, 2e-2)
     lib = Lb.lib()
     for force_valu in (0, 1):
         prev = lib.sel_tune(9, force_valu)
@@ -173,6 +176,8 @@ def test_dconv_layer_fwd_dgrad_wgrad(gpu, shape, dtype):
             d = DC._fwd_desc(sp, Bs, T, Ta, T_out, T_out, slope)
             y = torch.empty(Bs, T_out, cout, dtype=dt, device=gpu)
             DC.prim(d, x, DC.pack(sp, w, None, dt, 0), y, bias=b)
+            if dtype == "bf16":
+                check_bf16(y, ref, f"{tag} fwd (valu {force_valu})")
             e = ((y.double() - ref).norm() / ref.norm()).item()
             assert e <= tf, ("fwd", force_valu, e)
             # adjoint + weight gradient on gout = gy (no activation: the pre-activation gradient)
@@ -180,6 +185,8 @@ def test_dconv_layer_fwd_dgrad_wgrad(gpu, shape, dtype):
             db = DC._dgrad_desc(sp, Bs, Ta, T_out, T_out, slope, False)
             gin = torch.empty(Bs, Ta, cin, dtype=dt, device=gpu)
             DC.prim(db, g, DC.pack(sp, w, None, dt, 1), gin)
+            if dtype == "bf16":
+                check_bf16(gin[:, :T], xr.grad, f"{tag} dgrad (valu {force_valu})")
             e = ((gin[:, :T].double() - xr.grad).norm() / xr.grad.norm()).item()
             assert e <= tg, ("dgrad", force_valu, e)
             gw, _, gb = DC.wgrad(sp, d, g, x, w, None, True, True)
