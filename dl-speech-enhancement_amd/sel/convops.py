@@ -263,10 +263,13 @@ def _optimizer_stepped(optimizer, args, kwargs):
 _register_optimizer_step_post_hook(_optimizer_stepped)
 
 
-def prim(desc, x, wp, bias=None, aux=None, res=None, out_dtype=None):
-    """The conv primitive; x is (rows, C) channels-last (any leading shape)."""
-    out_dtype = out_dtype or x.dtype
-    out = torch.empty((desc.rows, desc.N), dtype=out_dtype, device=x.device)
+def prim(desc, x, wp, bias=None, aux=None, res=None, out_dtype=None, out=None):
+    """The conv primitive; x is (rows, C) channels-last (any leading shape).
+    out: a contiguous (rows, N) tensor to write into (its dtype is the output dtype)."""
+    out_dtype = out.dtype if out is not None else out_dtype or x.dtype
+    if out is None:
+        out = torch.empty((desc.rows, desc.N), dtype=out_dtype, device=x.device)
+    assert out.is_contiguous() and out.shape == (desc.rows, desc.N) and out.device == x.device
     for t in (aux, res):
         if t is not None:
             assert t.dtype == out_dtype and t.is_contiguous() and t.numel() == out.numel()
@@ -278,8 +281,9 @@ def prim(desc, x, wp, bias=None, aux=None, res=None, out_dtype=None):
 
 
 def fwd_kernel_name(desc, in_dtype, out_dtype, has_epilogue=False):
-    """rocprof name fragment of the kernel instance a launch uses."""
-    kid = L.lib().sel_conv_fwd_kernel_id(ctypes.byref(desc), _code(in_dtype), _code(out_dtype), int(has_epilogue))
+    """rocprof name fragment of the kernel instance a launch uses (a host
+    decision: needs the library, not a GPU)."""
+    kid = L.load().sel_conv_fwd_kernel_id(ctypes.byref(desc), _code(in_dtype), _code(out_dtype), int(has_epilogue))
     if kid < 0:
         return f"k_conv_fwd<{in_dtype}>"
     if kid >= 10 ** 9:  # weight-stationary thin kernel: 1e9 + E*5e8 + ((R/32*1000 + C)*1000 + N)*10 + K
@@ -289,9 +293,12 @@ def fwd_kernel_name(desc, in_dtype, out_dtype, has_epilogue=False):
         return f"k_conv_thin_bf16<{c}, {n}, {k}, {r}, {'true' if e else 'false'}>"
     to = "bf16" if out_dtype == torch.bfloat16 else "float"
     if kid >= 94 * 10 ** 7:  # sample-tile warp-specialised kernel (conv_wss.hip): 9.4e8 + 1e6 (SPT-1) + 1e4 BN + 10 S + K
+        # (BN = 128 carries into the SPT digit: the field above 1e4 is 100 (SPT - 1) + BN, BN in {64, 128})
         r = kid - 94 * 10 ** 7
-        spt, r = r // 10 ** 6 + 1, r % 10 ** 6
-        return f"k_conv_wss<{r % 10}, {(r // 10) % 1000}, {r // 10000}, {to}" + (f", {spt}>" if spt > 1 else ">")
+        f = r // 10 ** 4
+        bn = 128 if f % 100 == 28 else 64
+        spt = (f - bn) // 100 + 1
+        return f"k_conv_wss<{r % 10}, {(r // 10) % 1000}, {bn}, {to}" + (f", {spt}>" if spt > 1 else ">")
     if kid >= 93 * 10 ** 7:  # pointwise (1x1) weight-stationary kernel: 9.3e8 + N
         n = kid - 93 * 10 ** 7
         return f"k_pw_bf16<{n}, {n}"

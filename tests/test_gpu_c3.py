@@ -29,6 +29,8 @@ import zlib
 import pytest
 import torch
 
+from conv_cases import _check, _operands, _ref  # the fp64 primitive and the bf16 bound (tests/conv_cases.py)
+
 pytestmark = pytest.mark.gpu
 
 B = 64
@@ -82,51 +84,6 @@ def _ragged(gpu, CO, Bs, out32):
         ref = _ref(x, wp, d, Bs, b)
         got = CO.prim(d, x, wp, bias=b, out_dtype=od)
         _check(got, ref, (Bs, C, N, K, dil, mode, out32))
-
-
-def _ref(x, wp, d, B_, bias=None, aux=None, res=None):
-    """fp64 primitive on the same (bf16) operands: out[b,t,n] = sum_k,c
-    act(x)[b, t + k*dil - pad, c] * wp[n,k,c] (+ bias, * ELU'(aux), + res)."""
-    T, C, N, K = d.T, d.C, d.N, d.K
-    xa = x.double().view(B_, T, C)
-    if d.in_elu:
-        xa = torch.where(xa > 0, xa, torch.expm1(xa)).to(torch.bfloat16).double()
-    out = torch.zeros(B_, T, N, dtype=torch.float64, device=x.device)
-    w = wp.double()
-    for k in range(K):
-        idx = torch.arange(T, device=x.device) + k * d.dil - d.pad
-        if d.pad_mode == 0:
-            ok = (idx >= 0) & (idx < T)
-            xs = torch.zeros(B_, T, C, dtype=torch.float64, device=x.device)
-            xs[:, ok] = xa[:, idx[ok]]
-        else:
-            xs = xa[:, idx.clamp(0, T - 1)]
-        out += torch.einsum("btc,nc->btn", xs, w[:, k, :])
-    out = out.view(B_ * T, N)
-    if bias is not None:
-        out += bias.double().repeat(N // bias.numel())
-    if aux is not None:
-        out *= torch.where(aux.double() > 0, 1.0, torch.exp(aux.double()))
-    if res is not None:
-        out += res.double()
-    return out
-
-
-def _check(got, ref, what):
-    g = got.double()
-    e = ((g - ref).norm() / ref.norm()).item()
-    assert e <= 4e-3, (what, e)
-    bad = (g - ref).abs() > 8e-3 * ref.abs() + 2e-3 * ref.abs().max()
-    assert not bad.any(), (what, int(bad.sum()), (g - ref).abs().max().item())
-
-
-def _operands(d, gen, dev, aux, res):
-    x = (0.5 * torch.randn(d.rows, d.C, generator=gen, device=dev)).to(torch.bfloat16)
-    wp = (torch.randn(d.N, d.K, d.C, generator=gen, device=dev) / (d.K * d.C) ** 0.5).to(torch.bfloat16)
-    b = torch.randn(d.bias_period, generator=gen, device=dev) if d.bias_period else None
-    a_ = torch.randn(d.rows, d.N, generator=gen, device=dev).to(torch.bfloat16) if aux else None
-    r_ = torch.randn(d.rows, d.N, generator=gen, device=dev).to(torch.bfloat16) if res else None
-    return x, wp, b, a_, r_
 
 
 @pytest.mark.parametrize("form", ["fwd", "dgrad"])
