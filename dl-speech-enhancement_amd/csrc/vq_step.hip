@@ -26,6 +26,13 @@
 // lives, also shifts it into the row's bit-packed record and stores the bytes
 // that fill; the lookup has one (sel_rvq_lookup_wire_step) that takes its ids
 // out of such records instead of an int64 buffer.  A row owns its bytes.
+//
+// Datagrams (wire version 2): a third instance of each kernel (DGRAM:
+// sel_rvq_step_dgram, sel_rvq_lookup_dgram_step).  The quantizer stops its chain
+// after the sample's stage budget, read from device memory, and writes a header
+// and truncated records into the sample's region; the lookup reads the stage
+// count from the header and, for a sample that is lost, sums the record its
+// slot holds from the last valid hop.  The arithmetic is the one body above.
 #include <algorithm>
 
 #include "sel_common.h"
@@ -86,6 +93,7 @@ template <> struct WirePack<true> {
   int bits;
   __device__ __forceinline__ WirePack(const WireDst<true>& w, int64_t row)
       : p(w.wire + row * w.frame_bytes), acc(0), fill(0), bits(w.bits) {}
+  __device__ __forceinline__ WirePack(uint8_t* record, int bits_) : p(record), acc(0), fill(0), bits(bits_) {}
   __device__ __forceinline__ void put(int k, bool writer) {
     acc |= uint64_t(uint32_t(k)) << fill;
     fill += bits;
@@ -100,6 +108,48 @@ template <> struct WirePack<true> {
     if (fill > 0 && writer) *p = uint8_t(acc);
   }
 };
+
+// ---- the datagram of a sample (include/sel.h, wire version 2): the header {2, s, seq low, seq
+// high} and the sample's rows_per_sample records of s <= S fields each, inside the sample's own
+// dgram_stride bytes.  The DGRAM instances take this in WireDst's place. ----
+__host__ __device__ __forceinline__ int64_t record_bytes(int stages, int bits) {
+  return (int64_t(stages) * bits + 7) / 8;
+}
+
+struct DgramDst {
+  uint8_t* dgram;         // sample i owns [i * stride, (i + 1) * stride)
+  int64_t stride;
+  const int32_t* stages;  // device, one per sample; null: S
+  const int32_t* seq;     // device, one per sample; null: 0
+  int bits;
+};
+template <bool WIRE, bool DGRAM> struct StepDst { using type = WireDst<WIRE>; };
+template <> struct StepDst<true, true> { using type = DgramDst; };
+
+// The row's packer and the stages it runs.  The budget comes from memory but is the same in the
+// whole block: through readfirstlane it is a scalar, so the stage loop and the prefetch branch
+// that test it stay scalar branches.  The block of a sample's first row writes the header.
+template <bool WIRE, bool DGRAM>
+__device__ __forceinline__ WirePack<WIRE> open_pack(const typename StepDst<WIRE, DGRAM>::type& w, int64_t row, int T,
+                                                    int S, int& ns) {
+  if constexpr (DGRAM) {
+    const int64_t i = row / T;
+    const int r = int(row - i * T);
+    const int budget = w.stages ? w.stages[i] : S;
+    ns = __builtin_amdgcn_readfirstlane(min(max(budget, 1), S));
+    uint8_t* base = w.dgram + i * w.stride;
+    if (r == 0 && threadIdx.x == 0) {
+      const uint32_t q = w.seq ? uint32_t(w.seq[i]) : 0u;
+      base[0] = uint8_t(SEL_DGRAM_VERSION);
+      base[1] = uint8_t(ns);
+      base[2] = uint8_t(q);
+      base[3] = uint8_t(q >> 8);
+    }
+    return WirePack<true>(base + SEL_DGRAM_HEADER_BYTES + r * record_bytes(ns, w.bits), w.bits);
+  } else {
+    return WirePack<WIRE>(w, row);
+  }
+}
 
 // What both quantize kernels do once every thread holds its best (distance, code):
 // the block argmin (NW waves), then the first wave applies the pick to the row.
@@ -140,12 +190,12 @@ __device__ __forceinline__ void pick_and_update(float bd, int bk, int D, int K, 
   __syncthreads();
 }
 
-template <bool WIRE>
+template <bool WIRE, bool DGRAM = false>
 __global__ __launch_bounds__(COL_T) void k_rvq_step_col(const float* __restrict__ z, int64_t rows, int T,
                                                         const float* __restrict__ embeds, int S,
                                                         const int32_t* __restrict__ n_active, int cap, int flatten,
                                                         int64_t* __restrict__ idx, float* __restrict__ zq,
-                                                        WireDst<WIRE> wire) {
+                                                        typename StepDst<WIRE, DGRAM>::type wire) {
   constexpr int D = COL_D, K = COL_K, NW = COL_T / 64, C = COL_K / COL_T;
   __shared__ __align__(16) float res[D];
   __shared__ float acc[D];
@@ -155,7 +205,8 @@ __global__ __launch_bounds__(COL_T) void k_rvq_step_col(const float* __restrict_
   const int64_t row = blockIdx.x;
   if (row >= active_rows(n_active, cap, T, rows)) return;  // block-uniform
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  WirePack<WIRE> pack(wire, row);
+  int ns = S;  // the stages this row runs: all of them, or (DGRAM) its sample's budget
+  WirePack<WIRE> pack = open_pack<WIRE, DGRAM>(wire, row, T, S, ns);
 
   // One stage's codebook as a buffer resource: a load is then one VGPR byte
   // offset (the thread's code pair) plus a scalar offset (the row d) -- 64
@@ -180,7 +231,7 @@ __global__ __launch_bounds__(COL_T) void k_rvq_step_col(const float* __restrict_
   }
   __syncthreads();
 
-  for (int s = 0; s < S; ++s) {
+  for (int s = 0; s < ns; ++s) {
     const float* __restrict__ E = embeds + int64_t(s) * D * K;
     if (wave == 0) {
       float v = 0.f;
@@ -209,7 +260,7 @@ __global__ __launch_bounds__(COL_T) void k_rvq_step_col(const float* __restrict_
     // both stages' columns are live at once)
 #pragma unroll
     for (int j = 0; j < C; ++j) asm volatile("" : "+v"(dot[j]), "+v"(en[j]) : : "memory");
-    if (s + 1 < S) load_cols(s + 1, e);
+    if (s + 1 < ns) load_cols(s + 1, e);
     __syncthreads();
     float bd = __builtin_inff();
     int bk = 0x7fffffff;
@@ -226,15 +277,19 @@ __global__ __launch_bounds__(COL_T) void k_rvq_step_col(const float* __restrict_
                               pack);
   }
   if constexpr (WIRE) pack.finish(tid == 0);
+  if constexpr (DGRAM) {  // the stages not run: ids the lookup skips
+    if (idx)
+      for (int s = ns + tid; s < S; s += COL_T) idx[int64_t(s) * rows + row] = -1;
+  }
   if (zq && tid < D) zq[row * D + tid] = acc[tid];
 }
 
-template <bool WIRE>
+template <bool WIRE, bool DGRAM = false>
 __global__ __launch_bounds__(ANY_T) void k_rvq_step_any(const float* __restrict__ z, int64_t rows, int T, int D,
                                                         const float* __restrict__ embeds, int S, int K,
                                                         const int32_t* __restrict__ n_active, int cap, int flatten,
                                                         int64_t* __restrict__ idx, float* __restrict__ zq,
-                                                        WireDst<WIRE> wire) {
+                                                        typename StepDst<WIRE, DGRAM>::type wire) {
   constexpr int NW = ANY_T / 64;
   __shared__ float res[MAXD];
   __shared__ float acc[MAXD];
@@ -244,14 +299,15 @@ __global__ __launch_bounds__(ANY_T) void k_rvq_step_any(const float* __restrict_
   const int64_t row = blockIdx.x;
   if (row >= active_rows(n_active, cap, T, rows)) return;  // block-uniform
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  WirePack<WIRE> pack(wire, row);
+  int ns = S;  // the stages this row runs: all of them, or (DGRAM) its sample's budget
+  WirePack<WIRE> pack = open_pack<WIRE, DGRAM>(wire, row, T, S, ns);
   for (int d = tid; d < D; d += ANY_T) {
     res[d] = z[row * D + d];
     acc[d] = 0.f;
   }
   __syncthreads();
 
-  for (int s = 0; s < S; ++s) {
+  for (int s = 0; s < ns; ++s) {
     const float* __restrict__ E = embeds + int64_t(s) * D * K;
     if (wave == 0) {
       float v = 0.f;
@@ -298,6 +354,10 @@ __global__ __launch_bounds__(ANY_T) void k_rvq_step_any(const float* __restrict_
                               pack);
   }
   if constexpr (WIRE) pack.finish(tid == 0);
+  if constexpr (DGRAM) {
+    if (idx)
+      for (int s = ns + tid; s < S; s += ANY_T) idx[int64_t(s) * rows + row] = -1;
+  }
   if (zq)
     for (int d = tid; d < D; d += ANY_T) zq[row * D + d] = acc[d];
 }
@@ -330,9 +390,27 @@ template <> struct WireSrc<true> {
   int K, bits;
 };
 
+// DGRAM: the records come out of the samples' datagrams, or, for a sample that is
+// lost (flagged, or with a header this receiver refuses), out of the record its slot
+// holds from the last valid hop: hold row = {stages held (0: none), that record}.
+struct DgramSrc {
+  const uint8_t* dgram;  // sample i owns [i * stride, (i + 1) * stride)
+  int64_t stride;
+  const int32_t* slots;  // device, one per sample; null: slot i
+  const int32_t* lost;   // device, one per sample; null: none
+  uint8_t* hold;         // (nslots, hold_stride); may be null
+  int64_t hold_stride;
+  int nslots;
+  int64_t* idx_out;
+  int K, bits;
+};
+template <bool WIRE, bool DGRAM> struct LookupSrc { using type = WireSrc<WIRE>; };
+template <> struct LookupSrc<true, true> { using type = DgramSrc; };
+
 // V = 4: one thread per 4 channels (D % 4 == 0, 16-byte aligned operands); V = 1: per channel
-template <typename TO, int V, bool WIRE>
-__global__ __launch_bounds__(LK_T) void k_rvq_lookup_step(LookupArgs a, TO* __restrict__ out, WireSrc<WIRE> w) {
+template <typename TO, int V, bool WIRE, bool DGRAM = false>
+__global__ __launch_bounds__(LK_T) void k_rvq_lookup_step(LookupArgs a, TO* __restrict__ out,
+                                                          typename LookupSrc<WIRE, DGRAM>::type w) {
   const int per_row = a.D / V;
   const int64_t live = active_rows(a.n_active, a.cap, a.T, a.rows);
   const int64_t i0 = int64_t(blockIdx.x) * LK_T;
@@ -349,11 +427,39 @@ __global__ __launch_bounds__(LK_T) void k_rvq_lookup_step(LookupArgs a, TO* __re
   int64_t left = 0;
   uint64_t held = 0;
   int fill = 0;
-  if constexpr (WIRE) {
+  int ns = a.S;  // the stages of this row's record
+  if constexpr (DGRAM) {
+    const int64_t smp = row / a.T;
+    const int r = int(row - smp * a.T);
+    const uint8_t* base = w.dgram + smp * w.stride;
+    const int slot = w.slots ? w.slots[smp] : int(smp);
+    const bool held = w.hold && unsigned(slot) < unsigned(w.nslots);  // else: lost with nothing held
+    int got = 0;  // the header's stage count; a flagged sample's bytes are not looked at
+    if (!w.lost || w.lost[smp] == 0) {
+      if (base[0] == SEL_DGRAM_VERSION) got = base[1];
+    }
+    if (got >= 1 && got <= a.S) {  // valid: the row's own record; the last row's is kept
+      ns = got;
+      left = record_bytes(ns, w.bits);
+      p = base + SEL_DGRAM_HEADER_BYTES + r * left;
+      if (held && d0 == 0 && r == a.T - 1) {
+        uint8_t* h = w.hold + slot * w.hold_stride;
+        h[0] = uint8_t(ns);
+        for (int64_t b = 0; b < left; ++b) h[1 + b] = p[b];
+      }
+    } else if (held) {  // lost: every row decodes the held record; hold is only read
+      const uint8_t* h = w.hold + slot * w.hold_stride;
+      ns = min(int(h[0]), a.S);
+      left = record_bytes(ns, w.bits);
+      p = h + 1;
+    } else {
+      ns = 0;  // the empty sum
+    }
+  } else if constexpr (WIRE) {
     p = w.wire + row * w.frame_bytes;
     left = w.frame_bytes;
   }
-  for (int s = 0; s < a.S; ++s) {
+  for (int s = 0; s < ns; ++s) {
     int64_t id;
     if constexpr (WIRE) {
       while (fill < w.bits && left > 0) {  // never beyond the row's own bytes
@@ -381,6 +487,10 @@ __global__ __launch_bounds__(LK_T) void k_rvq_lookup_step(LookupArgs a, TO* __re
 #pragma unroll
     for (int j = 0; j < V; ++j) acc[j] = first ? v[j] : __fadd_rn(acc[j], v[j]);
     first = false;
+  }
+  if constexpr (DGRAM) {  // the fields that are not there
+    if (w.idx_out && d0 == 0)
+      for (int s = ns; s < a.S; ++s) w.idx_out[int64_t(s) * a.rows + row] = -1;
   }
   if (a.mean) {
 #pragma unroll
@@ -410,11 +520,17 @@ using namespace sel::vqstep;
 
 namespace {
 
-// sel_rvq_step and sel_rvq_step_wire: one set of checks, one dispatch
-template <bool WIRE>
+struct DgramCtl {  // what sel_rvq_step_dgram passes beside sel_rvq_step_wire's arguments
+  const int32_t* stages;
+  const int32_t* seq;
+  int64_t stride;
+};
+
+// sel_rvq_step, sel_rvq_step_wire and sel_rvq_step_dgram: one set of checks, one dispatch
+template <bool WIRE, bool DGRAM = false>
 int rvq_step_launch(const char* who, const float* z, int rows, int rows_per_sample, int D, const float* embeds, int S,
                     int K, const int32_t* n_active, int flatten, int64_t* idx, float* zq, uint8_t* wire,
-                    sel_stream_t stream) {
+                    sel_stream_t stream, DgramCtl g = {}) {
   SEL_REQUIRE(rows >= 1 && rows_per_sample >= 1 && rows % rows_per_sample == 0, SEL_ERR_ARG,
               "%s: rows (%d) must be a positive multiple of rows_per_sample (%d)", who, rows, rows_per_sample);
   SEL_REQUIRE(D > 0 && D <= MAXD && K > 0 && S > 0, SEL_ERR_ARG, "%s: bad shape D=%d (1..%d) K=%d S=%d", who, D, MAXD,
@@ -424,32 +540,41 @@ int rvq_step_launch(const char* who, const float* z, int rows, int rows_per_samp
   else
     SEL_REQUIRE(z && embeds && idx, SEL_ERR_ARG, "%s: null z / embeds / idx", who);
   SEL_REQUIRE(zq != z, SEL_ERR_ARG, "%s: zq aliases z", who);
-  WireDst<WIRE> w;
+  typename StepDst<WIRE, DGRAM>::type w;
   if constexpr (WIRE) {
     const int bits = wire_bits(K);
     SEL_REQUIRE(bits <= 31 && (int64_t(1) << bits) >= K, SEL_ERR_ARG, "%s: K=%d needs more than 31 bits per field", who,
                 K);
     SEL_REQUIRE(int64_t(S) * K <= (int64_t(1) << 40), SEL_ERR_ARG, "%s: S*K = %lld ids out of range", who,
                 (long long)(int64_t(S) * K));
-    w.wire = wire;
-    w.frame_bytes = (int64_t(S) * bits + 7) / 8;
-    w.bits = bits;
+    if constexpr (DGRAM) {
+      SEL_REQUIRE(S <= 255, SEL_ERR_ARG, "%s: S=%d does not fit the header's stage byte (<= 255)", who, S);
+      const int64_t need = SEL_DGRAM_HEADER_BYTES + rows_per_sample * record_bytes(S, bits);
+      SEL_REQUIRE(g.stride >= need, SEL_ERR_ARG, "%s: dgram_stride %lld is below the full datagram's %lld bytes", who,
+                  (long long)g.stride, (long long)need);
+      w = DgramDst{wire, g.stride, g.stages, g.seq, bits};
+    } else {
+      w.wire = wire;
+      w.frame_bytes = (int64_t(S) * bits + 7) / 8;
+      w.bits = bits;
+    }
   }
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int cap = rows / rows_per_sample;
   if (D == COL_D && K == COL_K)
-    hipLaunchKernelGGL(k_rvq_step_col<WIRE>, dim3(unsigned(rows)), dim3(COL_T), 0, s, z, int64_t(rows),
+    hipLaunchKernelGGL((k_rvq_step_col<WIRE, DGRAM>), dim3(unsigned(rows)), dim3(COL_T), 0, s, z, int64_t(rows),
                        rows_per_sample, embeds, S, n_active, cap, flatten, idx, zq, w);
   else
-    hipLaunchKernelGGL(k_rvq_step_any<WIRE>, dim3(unsigned(rows)), dim3(ANY_T), 0, s, z, int64_t(rows),
+    hipLaunchKernelGGL((k_rvq_step_any<WIRE, DGRAM>), dim3(unsigned(rows)), dim3(ANY_T), 0, s, z, int64_t(rows),
                        rows_per_sample, D, embeds, S, K, n_active, cap, flatten, idx, zq, w);
   SEL_LAUNCH_CHECK();
   return SEL_OK;
 }
 
 // sel_rvq_lookup_step and sel_rvq_lookup_wire_step: idx, or the packed records of K-code stages
-template <bool WIRE>
-int rvq_lookup_launch(const char* who, const int64_t* idx, WireSrc<WIRE> w, int rows, int rows_per_sample, int S,
+template <bool WIRE, bool DGRAM = false>
+int rvq_lookup_launch(const char* who, const int64_t* idx, typename LookupSrc<WIRE, DGRAM>::type w, int rows,
+                      int rows_per_sample, int S,
                       int64_t ncodes, int D, const float* codebook, const float* mean, const float* scale,
                       const int32_t* n_active, int out_dtype, void* out, sel_stream_t stream) {
   SEL_REQUIRE(rows >= 1 && rows_per_sample >= 1 && rows % rows_per_sample == 0, SEL_ERR_ARG,
@@ -458,7 +583,15 @@ int rvq_lookup_launch(const char* who, const int64_t* idx, WireSrc<WIRE> w, int 
               (long long)ncodes);
   SEL_REQUIRE(ncodes <= (int64_t(1) << 40) / D, SEL_ERR_ARG, "%s: codebook of %lld x %d out of range", who,
               (long long)ncodes, D);
-  if constexpr (WIRE)
+  if constexpr (DGRAM) {
+    SEL_REQUIRE(w.dgram && codebook && out, SEL_ERR_ARG, "%s: null dgram / codebook / out", who);
+    const int64_t need = SEL_DGRAM_HEADER_BYTES + rows_per_sample * record_bytes(S, w.bits);
+    SEL_REQUIRE(w.stride >= need, SEL_ERR_ARG, "%s: dgram_stride %lld is below the full datagram's %lld bytes", who,
+                (long long)w.stride, (long long)need);
+    SEL_REQUIRE(!w.hold || (w.hold_stride >= 1 + record_bytes(S, w.bits) && w.nslots >= 1), SEL_ERR_ARG,
+                "%s: hold rows of %lld bytes x %d slots, a row needs %lld and one slot at least", who,
+                (long long)w.hold_stride, w.nslots, (long long)(1 + record_bytes(S, w.bits)));
+  } else if constexpr (WIRE)
     SEL_REQUIRE(w.wire && codebook && out, SEL_ERR_ARG, "%s: null wire / codebook / out", who);
   else
     SEL_REQUIRE(idx && codebook && out, SEL_ERR_ARG, "%s: null idx / codebook / out", who);
@@ -474,11 +607,11 @@ int rvq_lookup_launch(const char* who, const int64_t* idx, WireSrc<WIRE> w, int 
   SEL_REQUIRE(threads / LK_T < (int64_t(1) << 31) - 1, SEL_ERR_ARG, "%s: rows * D out of range", who);
   const dim3 grid(unsigned((threads + LK_T - 1) / LK_T));
   if (out_dtype == SEL_F32) {
-    if (vec) hipLaunchKernelGGL((k_rvq_lookup_step<float, 4, WIRE>), grid, dim3(LK_T), 0, s, a, static_cast<float*>(out), w);
-    else hipLaunchKernelGGL((k_rvq_lookup_step<float, 1, WIRE>), grid, dim3(LK_T), 0, s, a, static_cast<float*>(out), w);
+    if (vec) hipLaunchKernelGGL((k_rvq_lookup_step<float, 4, WIRE, DGRAM>), grid, dim3(LK_T), 0, s, a, static_cast<float*>(out), w);
+    else hipLaunchKernelGGL((k_rvq_lookup_step<float, 1, WIRE, DGRAM>), grid, dim3(LK_T), 0, s, a, static_cast<float*>(out), w);
   } else {
-    if (vec) hipLaunchKernelGGL((k_rvq_lookup_step<__bf16, 4, WIRE>), grid, dim3(LK_T), 0, s, a, static_cast<__bf16*>(out), w);
-    else hipLaunchKernelGGL((k_rvq_lookup_step<__bf16, 1, WIRE>), grid, dim3(LK_T), 0, s, a, static_cast<__bf16*>(out), w);
+    if (vec) hipLaunchKernelGGL((k_rvq_lookup_step<__bf16, 4, WIRE, DGRAM>), grid, dim3(LK_T), 0, s, a, static_cast<__bf16*>(out), w);
+    else hipLaunchKernelGGL((k_rvq_lookup_step<__bf16, 1, WIRE, DGRAM>), grid, dim3(LK_T), 0, s, a, static_cast<__bf16*>(out), w);
   }
   SEL_LAUNCH_CHECK();
   return SEL_OK;
@@ -520,6 +653,27 @@ int sel_rvq_lookup_wire_step(const uint8_t* wire, int rows, int rows_per_sample,
   WireSrc<true> w{wire, idx_out, (int64_t(S) * bits + 7) / 8, K, bits};
   return rvq_lookup_launch<true>(who, nullptr, w, rows, rows_per_sample, S, int64_t(S) * K, D, codebook, mean, scale,
                                  n_active, out_dtype, out, stream);
+}
+
+int sel_rvq_step_dgram(const float* z, int rows, int rows_per_sample, int D, const float* embeds, int S, int K,
+                       const int32_t* n_active, const int32_t* stages, const int32_t* seq, int flatten, int64_t* idx,
+                       float* zq, uint8_t* dgram, int64_t dgram_stride, sel_stream_t stream) {
+  return rvq_step_launch<true, true>("sel_rvq_step_dgram", z, rows, rows_per_sample, D, embeds, S, K, n_active,
+                                     flatten, idx, zq, dgram, stream, DgramCtl{stages, seq, dgram_stride});
+}
+
+int sel_rvq_lookup_dgram_step(const uint8_t* dgram, int64_t dgram_stride, int rows, int rows_per_sample, int S, int K,
+                              int D, const float* codebook, const float* mean, const float* scale,
+                              const int32_t* n_active, const int32_t* slots, const int32_t* lost, uint8_t* hold,
+                              int64_t hold_stride, int nslots, int out_dtype, void* out, int64_t* idx_out,
+                              sel_stream_t stream) {
+  const char* who = "sel_rvq_lookup_dgram_step";
+  SEL_REQUIRE(S > 0 && S <= 255 && K > 0, SEL_ERR_ARG, "%s: bad shape S=%d (1..255) K=%d", who, S, K);
+  const int bits = wire_bits(K);
+  SEL_REQUIRE(bits <= 31 && (int64_t(1) << bits) >= K, SEL_ERR_ARG, "%s: K=%d needs more than 31 bits per field", who, K);
+  DgramSrc w{dgram, dgram_stride, slots, lost, hold, hold_stride, nslots, idx_out, K, bits};
+  return rvq_lookup_launch<true, true>(who, nullptr, w, rows, rows_per_sample, S, int64_t(S) * K, D, codebook, mean,
+                                       scale, n_active, out_dtype, out, stream);
 }
 
 }  // extern "C"

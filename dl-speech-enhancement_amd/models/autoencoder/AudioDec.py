@@ -99,28 +99,31 @@ class StreamGenerator(Generator):
     def decode(self, zq):
         return self.decoder.decode(zq.transpose(2, 1))
 
-    def session(self, batch=1, chunk=300, graph=True, codes=False, wire=False):
+    def session(self, batch=1, chunk=300, graph=True, codes=False, wire=False, datagrams=False):
         """An opt-in sel.streaming.StreamSession over this generator: fixed state,
         one step launch per layer, each hop replayed as a graph.  ``codes=True``
         also calls ``enable_codes()``: ``transmit`` / ``receive`` with the
         quantizer and the lookup inside the hop.  ``wire=True`` (with ``codes``):
         ``enable_codes(wire=True)``, the packets of sel/wire.py inside the hop too
-        (``transmit_packets`` / ``receive_packets``)."""
+        (``transmit_packets`` / ``receive_packets``).  ``datagrams=True`` (with
+        ``codes``): ``enable_codes(datagrams=True)``, datagrams with a stage budget
+        per stream and loss concealment (``transmit_datagrams`` /
+        ``receive_datagrams``)."""
         from sel.streaming import StreamSession
         s = StreamSession(self, batch, chunk, graph)
         if codes:
-            s.enable_codes(wire=wire)
+            s.enable_codes(wire=wire, datagrams=datagrams)
         return s
 
-    def pool(self, capacity, chunk=300, graph=True, dtype=None, codes=False, wire=False):
+    def pool(self, capacity, chunk=300, graph=True, dtype=None, codes=False, wire=False, datagrams=False):
         """An opt-in sel.streaming.StreamPool over this generator: `capacity`
         independent streams that open, close and tick on their own, one batched
         hop per tick over the active ones.  ``codes=True`` also calls
-        ``enable_codes()``, with ``wire=True`` ``enable_codes(wire=True)``."""
+        ``enable_codes()``, with ``wire=True`` / ``datagrams=True`` passed on to it."""
         from sel.streaming import StreamPool
         p = StreamPool(self, capacity, chunk, graph, dtype)
         if codes:
-            p.enable_codes(wire=wire)
+            p.enable_codes(wire=wire, datagrams=datagrams)
         return p
 
     def reset_buffer(self):

@@ -225,27 +225,27 @@ class StreamGenerator(Generator):
                              out_dtype=torch.float32)
         return x.transpose(1, 2)
 
-    def session(self, batch=1, frames=1, graph=True, codes=False, wire=False):
+    def session(self, batch=1, frames=1, graph=True, codes=False, wire=False, datagrams=False):
         """An opt-in sel.streaming.VocoderSession over this generator: fixed state,
         one grouped step launch per conv, each hop of `frames` frames replayed as a graph.
         ``codes=True`` also calls ``enable_codes()``; a vocoder has no codebooks of
         its own, so ``receive`` works once ``enable_codes(lookup_generator)`` has
-        been given the encoder's generator.  ``wire=True`` (with ``codes``) is
-        passed on to ``enable_codes``."""
+        been given the encoder's generator.  ``wire=True`` and ``datagrams=True``
+        (with ``codes``) are passed on to ``enable_codes``."""
         from sel.streaming import VocoderSession
         s = VocoderSession(self, batch, frames, graph)
         if codes:
-            s.enable_codes(wire=wire)
+            s.enable_codes(wire=wire, datagrams=datagrams)
         return s
 
-    def pool(self, capacity, frames=1, graph=True, dtype=None, codes=False, wire=False):
+    def pool(self, capacity, frames=1, graph=True, dtype=None, codes=False, wire=False, datagrams=False):
         """An opt-in sel.streaming.VocoderPool over this generator: `capacity`
         independent streams, one batched hop per tick over the active ones.
-        ``codes=True`` and ``wire=True`` as in ``session``."""
+        ``codes=True``, ``wire=True`` and ``datagrams=True`` as in ``session``."""
         from sel.streaming import VocoderPool
         p = VocoderPool(self, capacity, frames, graph, dtype)
         if codes:
-            p.enable_codes(wire=wire)
+            p.enable_codes(wire=wire, datagrams=datagrams)
         return p
 
     def reset_buffer(self):

@@ -71,6 +71,8 @@ SIGNATURES = {
     "sel_rvq_lookup_step": (I32, [P, I32, I32, I32, I64, I32, P, P, P, P, I32, P, P]),
     "sel_rvq_step_wire": (I32, [P, I32, I32, I32, P, I32, I32, P, I32, P, P, P, P]),
     "sel_rvq_lookup_wire_step": (I32, [P, I32, I32, I32, I32, I32, P, P, P, P, I32, P, P, P]),
+    "sel_rvq_step_dgram": (I32, [P, I32, I32, I32, P, I32, I32, P, P, P, I32, P, P, P, I64, P]),
+    "sel_rvq_lookup_dgram_step": (I32, [P, I64, I32, I32, I32, I32, I32, P, P, P, P, P, P, P, I64, I32, I32, P, P, P]),
     "sel_rvq_ema_workspace": (SZ, [I64, I32, I32, I32]),
     "sel_rvq_ema_update": (I32, [P, I64, I32, P, I32, I32, P, P, P, F32, F32, P, SZ, P]),
     "sel_rvq_ema_stats_floats": (SZ, [I32, I32, I32]),

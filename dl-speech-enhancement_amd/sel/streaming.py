@@ -33,6 +33,11 @@ then one replay from samples to code indices, ``receive`` one from code
 indices to samples.  ``enable_codes(wire=True)`` also puts the bytes of the
 wire format (sel/wire.py) inside the hop: ``transmit_packets`` is one replay from
 samples to packets, ``receive_packets`` one from packets to samples.
+``enable_codes(datagrams=True)`` adds what a sender puts on a network (wire
+version 2, ``sel.wire.DatagramFormat``): ``transmit_datagrams`` stops the
+quantizer after each stream's stage budget and writes a header with the stage
+count and the hop number; ``receive_datagrams`` decodes whatever stage count
+arrives and conceals a hop that did not, from the stream's last good record.
 """
 import functools
 
@@ -158,6 +163,41 @@ class _Half:
             self.launch_codes(self.pre_wire)
         return self.outs[-1]
 
+    # ---- datagrams inside the hop (enable_codes(datagrams=True)) ---------------------
+    pre_dgram = post_dgram = dgram_graph = dgram_buf = dgram_ctl = hold = None
+    dgram_staged = None       # sessions: the control words the device holds (None: unknown)
+
+    def add_datagrams(self, buf, ctl, pre=None, post=None, hold=None):
+        """A further launch list beside the others, ``pre -> steps -> commit`` (the
+        receiver: lookup_dgram_step out of ``buf``) or ``steps -> commit -> post``
+        (the transmitter: rvq_step_dgram into ``buf``), and for a captured half a
+        further graph.  ``ctl``: the device control words the new launch reads
+        (budgets and hop numbers, or loss flags), staged before every replay.
+        ``hold``: the receiver's per-stream held records.  As in ``add_codes`` only
+        the new stateless launch is warmed up and the capture executes nothing."""
+        self.dgram_buf, self.dgram_ctl, self.pre_dgram, self.post_dgram, self.hold = buf, ctl, pre, post, hold
+        self.dgram_graph = self.dgram_staged = None
+        if self.graph is not None:
+            (pre or post)()
+            torch.cuda.synchronize(self.inp.device)
+            self.dgram_graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.dgram_graph):
+                self.launch_dgram()
+
+    def launch_dgram(self):
+        if self.pre_dgram is not None:
+            self.pre_dgram()
+        self.launch()
+        if self.post_dgram is not None:
+            self.post_dgram()
+
+    def run_dgram(self):
+        if self.dgram_graph is not None:
+            self.dgram_graph.replay()
+        else:
+            self.launch_dgram()
+        return self.outs[-1]
+
 
 def _fill_idx(dst, idx, what):
     """idx (S, [batch,] frames) int64 -> the fixed (S, rows) buffer (or its first rows)."""
@@ -181,11 +221,13 @@ class _CodesMixin:
     quantizer behind the transmitter's hop and the codebook lookup in front of
     the receiver's, inside the hop's launch list (csrc/vq_step.hip)."""
     _tx = _rx = None          # the halves that carry codes once enable_codes ran
-    _codes_enabled = _wire_enabled = False
+    _codes_enabled = _wire_enabled = _dgram_enabled = False
     wire = None               # the WireFormat once enable_codes(wire=True) gave a half its packets
+    datagram = None           # the DatagramFormat once enable_codes(datagrams=True) gave a half its datagrams
+    _seq = _dstats = _dgram_stager = None
 
     @torch.no_grad()
-    def enable_codes(self, lookup_generator=None, wire=False):
+    def enable_codes(self, lookup_generator=None, wire=False, datagrams=False):
         """Put ``quantize`` behind ``encode`` and ``lookup`` in front of ``decode``:
         afterwards ``transmit`` is one replay from samples to code indices and
         ``receive`` one replay from code indices to samples.
@@ -206,11 +248,23 @@ class _CodesMixin:
         the indices (``transmit`` keeps its bits, ``transmit_packets`` returns the
         bytes of the same replay), and the receiver gets a third launch list and
         graph that looks the codes up straight out of the packet buffer
-        (``receive_packets``), with no int64 buffer in between."""
+        (``receive_packets``), with no int64 buffer in between.
+
+        ``datagrams=True`` adds wire version 2 (``self.datagram``, a
+        ``sel.wire.DatagramFormat``) beside whatever the other keywords built: a
+        further launch list and graph per half.  The transmitter's ends in
+        ``rvq_step_dgram``, whose chain stops after each stream's stage budget
+        (``transmit_datagrams(x, stages)``); the receiver's starts with
+        ``rvq_lookup_dgram_step``, which takes the stage count from each header and
+        conceals a hop that did not arrive by repeating the stream's last good
+        record (``receive_datagrams``).  Budgets, hop numbers and loss flags are
+        device words staged before the replay, so one graph serves every mix."""
         dev = self._dec.inp.device
         frames = self.plan.frames
-        self._tx = self._rx = self.wire = None
-        fmt = []
+        self._tx = self._rx = self.wire = self.datagram = None
+        self._seq = self._dstats = None
+        self._dgram_enabled = False
+        fmt, dfmt = [], []
         enc = getattr(self, "_enc", None)
         if enc is not None and self.plan.pqc:
             rvq = self.generator.quantizer.codebook
@@ -229,6 +283,19 @@ class _CodesMixin:
                               wire_buf=buf)
             else:
                 enc.add_codes(idx, post=functools.partial(SO.rvq_step, z, stack, idx, frames, count, True))
+            if datagrams:
+                dfmt.append(self._datagram_format(stack.shape[0], stack.shape[2], frames))
+                B = z.shape[0] // frames
+                dbuf = torch.zeros((B, dfmt[-1].stride), dtype=torch.uint8, device=dev)
+                ctl, (stages, seq) = self._dgram_words(enc, B, 2, dev)
+                post = functools.partial(SO.rvq_step_dgram, z, stack, dbuf, frames, count, stages, seq, True)
+                if count is None:
+                    # a session (no slot list to stage): the hop numbers advance on the device, behind
+                    # the launch that read them, so a steady budget needs no control copy per hop
+                    def post(launch=post, seq=seq):
+                        launch()
+                        seq.add_(1)
+                enc.add_datagrams(dbuf, ctl, post=post)
             self._tx = enc
         lg = lookup_generator if lookup_generator is not None else self.lookup_generator
         dec = self._dec
@@ -259,12 +326,134 @@ class _CodesMixin:
                                                          scale, count))
             else:
                 dec.add_codes(idx, pre=pre)
+            if datagrams:
+                if flat.shape[0] % S:
+                    raise L.SelError(f"sel: the lookup codebook's {flat.shape[0]} rows are not {S} stages of one size")
+                dfmt.append(self._datagram_format(S, flat.shape[0] // S, frames))
+                B = dec.inp.shape[0]
+                dbuf = torch.zeros((B, dfmt[-1].stride), dtype=torch.uint8, device=dev)
+                # a stream's last good record, at a fixed address: one row per batch stream / pool slot
+                hold = torch.zeros((B, 1 + dfmt[-1].frame_bytes()), dtype=torch.uint8, device=dev)
+                ctl, (lost,) = self._dgram_words(dec, B, 1, dev)
+                dec.add_datagrams(dbuf, ctl, hold=hold,
+                                  pre=functools.partial(SO.rvq_lookup_dgram_step, dbuf, flat, S, dec.inp, frames, mean,
+                                                        scale, count, getattr(dec, "slots", None), lost, hold))
             self._rx = dec
-        if len(fmt) == 2 and (fmt[0].codebooks, fmt[0].codebook_size) != (fmt[1].codebooks, fmt[1].codebook_size):
-            raise L.SelError(f"sel: the transmitter packs {fmt[0]!r}, the lookup codebook reads {fmt[1]!r}")
+        for f in (fmt, dfmt):
+            if len(f) == 2 and (f[0].codebooks, f[0].codebook_size) != (f[1].codebooks, f[1].codebook_size):
+                raise L.SelError(f"sel: the transmitter packs {f[0]!r}, the lookup codebook reads {f[1]!r}")
         if fmt:
             self.wire = fmt[0]
-        self._codes_enabled, self._wire_enabled = True, bool(wire)
+        if dfmt:
+            self.datagram = dfmt[0]
+            streams = self._dec.inp.shape[0]
+            self._seq = [0] * streams
+            self._dstats = [self._new_stats() for _ in range(streams)]
+        self._codes_enabled, self._wire_enabled, self._dgram_enabled = True, bool(wire), bool(datagrams)
+
+    # ---- datagrams: formats, control words, counters ----------------------------------------
+    @staticmethod
+    def _datagram_format(S, K, frames):
+        from .wire import DatagramFormat
+        try:
+            return DatagramFormat(S, K, frames)
+        except ValueError as e:
+            raise L.SelError(f"sel: enable_codes(datagrams=True): {e}") from None
+
+    def _dgram_words(self, half, B, arrays, device):
+        """The device control words of a half's datagram launch: ``arrays`` int32
+        arrays of B entries (one per stream) behind one another, so that one copy
+        stages them all -> (the tensor to stage into, the arrays).  A session has no
+        control words yet and gets a tensor of its own (pools: _PoolBase)."""
+        if self._dgram_stager is None:
+            self._dgram_stager = _Stager(2 * B, device)
+        ctl = torch.zeros(arrays * B, dtype=torch.int32, device=device)
+        return ctl, [ctl[i * B:(i + 1) * B] for i in range(arrays)]
+
+    @staticmethod
+    def _new_stats():
+        return dict(received=0, lost=0, refused=0, seq_gaps=0, concealed_run=0, stages=None, seq=None)
+
+    def _clear_stream(self, i):
+        """Stream i (a batch position, a pool slot) starts over: hop number 0, nothing held, counters at zero."""
+        if self._seq is not None:
+            self._seq[i] = 0
+            self._dstats[i] = self._new_stats()
+        if self._rx is not None and self._rx.hold is not None:
+            self._rx.hold[i].zero_()
+
+    def _stage_list(self, what, stages, n):
+        """``stages``: None (all), an int, or one int per stream, each in [1, S] -> a list of n ints."""
+        S = self.datagram.codebooks
+        if stages is None:
+            return [S] * n
+        if isinstance(stages, torch.Tensor):
+            if stages.dim() > 1 or stages.dtype not in (torch.int32, torch.int64):
+                raise L.SelError(f"sel: {what} takes stages as an int or {n} ints, got {stages.dtype} "
+                                 f"{tuple(stages.shape)}")
+            stages = stages.tolist()
+        raw = [stages] * n if isinstance(stages, int) and not isinstance(stages, bool) else list(stages) \
+            if isinstance(stages, (list, tuple)) else None
+        if raw is None or len(raw) != n:
+            raise L.SelError(f"sel: {what} takes stages as an int or {n} ints, got {stages!r}")
+        for s in raw:
+            if not isinstance(s, int) or isinstance(s, bool) or not 1 <= s <= S:
+                raise L.SelError(f"sel: {what}: a budget of {s!r} stages, the quantizer has 1..{S}")
+        return raw
+
+    def _take_datagrams(self, what, dst, p, lost, streams):
+        """Fill the fixed buffer's rows ``dst`` (n, stride) from ``p`` and return the n
+        loss flags, counting per stream.  ``p``: a device uint8 (n, stride) tensor
+        (``lost``: n flags or None), or a list of bytes-like / None entries, which
+        goes through ``DatagramFormat.assemble`` and one host-to-device copy."""
+        n, fmt = dst.shape[0], self.datagram
+        heads = [None] * n
+        refused = ()
+        if isinstance(p, torch.Tensor):
+            L.need_device(p)
+            if p.dtype != torch.uint8 or tuple(p.shape) != tuple(dst.shape):
+                raise L.SelError(f"sel: {what} takes uint8 datagrams of shape {tuple(dst.shape)}, got {p.dtype} "
+                                 f"{tuple(p.shape)}")
+            flags = self._flag_list(what, lost, n)
+            dst.copy_(p)
+        elif isinstance(p, (list, tuple)):
+            if len(p) != n or any(d is not None and not isinstance(d, (bytes, bytearray, memoryview)) for d in p):
+                raise L.SelError(f"sel: {what} takes {n} datagrams, each bytes-like or None")
+            buf, gone, refused = fmt.assemble(p)
+            flags = [int(a or b) for a, b in zip(gone, self._flag_list(what, lost, n))]
+            heads = [None if f else fmt.parse(d) for f, d in zip(gone, p)]
+            dst.copy_(buf)
+        else:
+            raise L.SelError(f"sel: {what} takes a device uint8 tensor or a list of bytes-like / None entries, got "
+                             f"{type(p).__name__}")
+        for j, (i, f) in enumerate(zip(streams, flags)):
+            st = self._dstats[i]
+            if f:
+                st["lost"] += 1
+                st["refused"] += int(j in refused)
+                st["concealed_run"] += 1
+                continue
+            st["received"] += 1
+            st["concealed_run"] = 0
+            if heads[j] is not None:                  # a device tensor's headers are not read back
+                s, q = heads[j]
+                if st["seq"] is not None:
+                    st["seq_gaps"] += (q - st["seq"] - 1) & 0xFFFF
+                st["stages"], st["seq"] = s, q
+        return flags
+
+    @staticmethod
+    def _flag_list(what, lost, n):
+        if lost is None:
+            return [0] * n
+        if isinstance(lost, torch.Tensor):
+            if lost.dim() != 1 or lost.dtype not in (torch.bool, torch.int32, torch.int64):
+                raise L.SelError(f"sel: {what} takes lost as {n} flags, got {lost.dtype} {tuple(lost.shape)}")
+            lost = lost.tolist()
+        if not isinstance(lost, (list, tuple)) or len(lost) != n or \
+                any(not isinstance(f, (bool, int)) for f in lost):
+            raise L.SelError(f"sel: {what} takes lost as {n} flags, got {lost!r}")
+        return [int(bool(f)) for f in lost]
 
     def _prepare_codes(self, half):
         """Before a half's new launch is warmed up and captured (pools: no active stream)."""
@@ -274,6 +463,8 @@ class _CodesMixin:
             raise L.SelError(f"sel: {which} needs enable_codes() first")
         if which.endswith("_packets") and not self._wire_enabled:
             raise L.SelError(f"sel: {which} needs enable_codes(wire=True) first")
+        if which.endswith("_datagrams") and not self._dgram_enabled:
+            raise L.SelError(f"sel: {which} needs enable_codes(datagrams=True) first")
         if which.startswith("transmit"):
             if self._tx is None:
                 raise L.SelError(f"sel: {which} needs a transmitter with PQC: without it (or on a vocoder) encode's "
@@ -421,6 +612,81 @@ class StreamSession(_CodesMixin):
         _fill_packets(half.wire_buf.view(pl.batch, self.wire.packet_bytes), p, "session receive_packets")
         return half.run_wire().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
 
+    # ---- the same in datagrams, wire version 2 (after enable_codes(datagrams=True)) -----
+    @torch.no_grad()
+    def transmit_datagrams(self, x, stages=None):
+        """x (batch, in_channels, chunk) -> (batch, stride) uint8, ``stride =
+        self.datagram.stride``: row i starts with stream i's datagram for this hop
+        -- the header with the stages carried and the stream's hop number (0 after
+        construction and ``reset()``, wrapping at 2^16), then the hop's records of
+        ``stages`` fields -- ``self.datagram.datagram_bytes(stages[i])`` bytes; the
+        bytes of a row beyond that are not written and keep what an earlier hop
+        left there.  ``stages``: an int or one int per stream in [1, codebooks],
+        default all; the quantizer's chain stops after that many stages.  One
+        replay, whatever the budgets: they are device words, staged in front of it
+        when they change (the hop numbers advance on the device, behind the
+        quantizer's launch).  A VIEW of a fixed buffer: a call invalidates the view the previous
+        ``transmit_datagrams`` returned and, like ``transmit``, ``encode``'s; the
+        views of ``transmit`` / ``transmit_packets`` stay valid."""
+        half = self._codes_half("transmit_datagrams")
+        pl = self.plan
+        L.need_device(x)
+        if tuple(x.shape) != (pl.batch, pl.in_channels, pl.chunk):
+            raise L.SelError(f"sel: session transmit_datagrams takes {(pl.batch, pl.in_channels, pl.chunk)}, got "
+                             f"{tuple(x.shape)}")
+        budgets = self._stage_list("session transmit_datagrams", stages, pl.batch)
+        self._stage_words(half, budgets + self._seq)
+        half.dgram_staged = None                         # unknown until the hop has run
+        half.inp.copy_(x.transpose(1, 2))
+        half.run_dgram()
+        # the hop's last launch added 1 to every hop number on the device: with the same budgets the
+        # next hop finds its words in place (at the 2^16 wrap they differ, and are staged again)
+        half.dgram_staged = budgets + [q + 1 for q in self._seq]
+        self._seq = [(q + 1) & 0xFFFF for q in self._seq]
+        return half.dgram_buf
+
+    @torch.no_grad()
+    def receive_datagrams(self, p, lost=None):
+        """The datagrams of one hop -> y, what ``receive`` returns for the ids in
+        them (-1 beyond the stages a datagram carries): one replay.  ``p``: a
+        device uint8 (batch, stride) tensor as ``transmit_datagrams`` returns it,
+        with ``lost``, one flag per stream, marking rows to disregard; or a list
+        of ``batch`` entries, bytes-like or None for a datagram that did not
+        arrive, which ``self.datagram.assemble`` turns into one host-to-device
+        copy.  A lost stream -- flagged, None, or with a header this receiver
+        refuses -- is concealed: every frame of the hop decodes the last frame's
+        record of the stream's last good datagram (nothing held yet: the empty
+        sum), so the decoder's carried state moves on.  Nothing is reordered: the
+        caller decides which datagram belongs to which hop.  ``datagram_stats()``
+        counts."""
+        half = self._codes_half("receive_datagrams")
+        pl = self.plan
+        flags = self._take_datagrams("session receive_datagrams", half.dgram_buf, p, lost, range(pl.batch))
+        self._stage_words(half, flags)
+        return half.run_dgram().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
+
+    def _stage_words(self, half, words):
+        """A session half's control words, staged as a pool's slot list is -- unless the
+        device already holds exactly these (a receiver that loses nothing stages nothing)."""
+        if half.dgram_staged != words:
+            self._dgram_stager.stage(half.dgram_ctl, words)
+            half.dgram_staged = words
+
+    def datagram_stats(self):
+        """Per stream, since construction / ``reset()``: hops ``received``, ``lost``
+        (``refused``: of those, the malformed ones), ``seq_gaps`` (hop numbers missing
+        between consecutive datagrams seen), ``concealed_run`` (the current run of
+        concealed hops) and the last datagram's ``stages`` and ``seq``.  Headers are
+        read on the host only: for datagrams given as a device tensor ``refused``,
+        ``seq_gaps``, ``stages`` and ``seq`` do not move."""
+        if not self._dgram_enabled:
+            raise L.SelError("sel: datagram_stats needs enable_codes(datagrams=True) first")
+        return [dict(s) for s in self._dstats]
+
+    def _reset_datagrams(self):
+        for i in range(len(self._seq or ())):
+            self._clear_stream(i)
+
     # ---- state ------------------------------------------------------------------
     def _layers(self):
         for half in (self._enc, self._dec):
@@ -436,6 +702,7 @@ class StreamSession(_CodesMixin):
     def reset(self):
         self._enc.zero()
         self._dec.zero()
+        self._reset_datagrams()
 
     @torch.no_grad()
     def load_state(self):
@@ -566,6 +833,11 @@ class VocoderSession(_CodesMixin):
     receive = StreamSession.receive
     transmit_packets = StreamSession.transmit_packets
     receive_packets = StreamSession.receive_packets
+    transmit_datagrams = StreamSession.transmit_datagrams
+    receive_datagrams = StreamSession.receive_datagrams
+    datagram_stats = StreamSession.datagram_stats
+    _reset_datagrams = StreamSession._reset_datagrams
+    _stage_words = StreamSession._stage_words
 
     # ---- state ------------------------------------------------------------------
     def _layers(self):
@@ -580,6 +852,7 @@ class VocoderSession(_CodesMixin):
     @torch.no_grad()
     def reset(self):
         self._dec.zero()
+        self._reset_datagrams()
 
     @torch.no_grad()
     def load_state(self):
@@ -638,7 +911,10 @@ class _PoolMixin:
     def _make_pool(self, capacity, device):
         self.capacity = capacity
         self.nslots = capacity + 1          # row `capacity` is the template
-        self.ctl = torch.zeros(1 + capacity, dtype=torch.int32, device=device)
+        # [n, slots...] and, behind them, room for two per-stream arrays of a datagram
+        # tick (budgets and hop numbers, or loss flags): one tensor, so one copy stages a tick
+        self.ctl_all = torch.zeros(1 + 3 * capacity, dtype=torch.int32, device=device)
+        self.ctl = self.ctl_all[:1 + capacity]
         self.n_active, self.slots = self.ctl[:1], self.ctl[1:]
         for lst in (self.carry, self.carry_out):
             for i, c in enumerate(lst):
@@ -677,9 +953,10 @@ class _PoolBase(_CodesMixin):
         self.capacity = int(capacity)
         self.table = SO.SlotTable(capacity)
         self._halves = halves
-        # the ring carries a tick's [n, slots...] (1 + capacity words) and open()'s
-        # three words below, whichever is longer (capacity 1: three)
-        self._stager = _Stager(max(3, 1 + self.capacity), device)
+        # the ring carries a tick's [n, slots...] (1 + capacity words; a datagram tick's
+        # two further arrays of capacity words) and open()'s three words below
+        self._stager = _Stager(1 + 3 * self.capacity, device)
+        self._dgram_stager = self._stager
         # opening a stream: [1, capacity (the template row), the new slot]
         self._open_ctl = torch.zeros(3, dtype=torch.int32, device=device)
         self._carries = [c for h in halves for c in h.carry if c is not None]
@@ -760,6 +1037,69 @@ class _PoolBase(_CodesMixin):
         out = half.run_wire()
         return out.view(self.capacity, pl.out_samples, pl.out_channels)[:n].transpose(1, 2)
 
+    # ---- the same in datagrams (after enable_codes(datagrams=True)) ------------------------------
+    def _dgram_words(self, half, B, arrays, device):
+        # behind the slot list, in the tensor the half's graphs already read: a tick is one copy
+        cap = self.capacity
+        views = [half.ctl_all[1 + (1 + i) * cap:1 + (2 + i) * cap] for i in range(arrays)]
+        return half.ctl_all[:1 + (1 + arrays) * cap], views
+
+    def _stage_dgram(self, half, slots, *arrays):
+        """[n, slots..., array 0..., array 1...], each padded to capacity, in one copy."""
+        pad = [0] * (self.capacity - len(slots))
+        words = [len(slots)] + slots + pad
+        for a in arrays:
+            words += a + pad
+        self._stager.stage(half.dgram_ctl, words)
+        return len(slots)
+
+    @torch.no_grad()
+    def transmit_datagrams(self, slots, x, stages=None):
+        """x (n, in_channels, chunk) for the n listed slots -> (n, stride) uint8, row i
+        starting with the datagram of ``slots[i]`` for this hop, as a session's
+        ``transmit_datagrams`` writes it; ``stages``: an int or one int per listed
+        slot.  A slot's hop number starts at 0 at ``open()``.  One replay and one
+        control copy, whatever the slots and budgets.  A VIEW of a fixed buffer: a
+        call invalidates the view of the previous ``transmit_datagrams`` (and
+        ``encode``'s); those of ``transmit`` / ``transmit_packets`` stay valid."""
+        half = self._codes_half("transmit_datagrams")
+        pl = self.plan
+        L.need_device(x)
+        if tuple(x.shape) != (len(slots), pl.in_channels, pl.chunk):
+            raise L.SelError(f"sel: pool transmit_datagrams takes {(len(slots), pl.in_channels, pl.chunk)} for "
+                             f"{len(slots)} slots, got {tuple(x.shape)}")
+        slots = self.table.check(slots)
+        budgets = self._stage_list("pool transmit_datagrams", stages, len(slots))
+        n = self._stage_dgram(half, slots, budgets, [self._seq[s] & 0xFFFF for s in slots])
+        for s in slots:
+            self._seq[s] += 1
+        half.inp[:n].copy_(x.transpose(1, 2))
+        half.run_dgram()
+        return half.dgram_buf[:n]
+
+    @torch.no_grad()
+    def receive_datagrams(self, slots, p, lost=None):
+        """The datagrams of one tick, entry i for ``slots[i]`` -> y (n, out_channels,
+        samples): a session's ``receive_datagrams`` per listed slot, each slot
+        concealing its own lost hops from its own held record (cleared at
+        ``open()``).  ``p``: a device uint8 (n, stride) tensor with optional
+        ``lost`` flags, or a list of n bytes-like / None entries.  One replay."""
+        half = self._codes_half("receive_datagrams")
+        pl = self.plan
+        slots = self.table.check(slots)
+        n = len(slots)
+        flags = self._take_datagrams(f"pool receive_datagrams for {n} slots", half.dgram_buf[:n], p, lost, slots)
+        self._stage_dgram(half, slots, flags)
+        out = half.run_dgram()
+        return out.view(self.capacity, pl.out_samples, pl.out_channels)[:n].transpose(1, 2)
+
+    def datagram_stats(self, slot):
+        """The counters of a session's ``datagram_stats()`` for one open slot, since its ``open()``."""
+        if not self._dgram_enabled:
+            raise L.SelError("sel: datagram_stats needs enable_codes(datagrams=True) first")
+        slot, = self.table.check([slot])
+        return dict(self._dstats[slot])
+
     def _layers(self):
         for half in self._halves:
             for st, c in zip(half.steps, half.carry):
@@ -774,6 +1114,7 @@ class _PoolBase(_CodesMixin):
             self._stager.stage(self._open_ctl, [1, self.capacity, slot])
             c = self._open_ctl
             SO.copy_slots([(t, t) for t in self._carries], c[1:2], c[2:3], c[0:1])
+            self._clear_stream(slot)    # hop number 0, and nothing held from the slot's previous stream
         except BaseException:
             self.table.close(slot)      # the slot is taken only once its state is in place
             raise

@@ -23,7 +23,10 @@ slot-indexed forms for stream pools (``sel.streaming.StreamPool``), and
 hop as stateless step launches (csrc/vq_step.hip), which
 ``sel.streaming``'s ``enable_codes`` puts inside the hop's launch list;
 ``rvq_step_wire`` / ``rvq_lookup_wire_step`` are the same launches writing and
-reading the packed records of the wire format (``sel.wire``).
+reading the packed records of the wire format (``sel.wire``), and
+``rvq_step_dgram`` / ``rvq_lookup_dgram_step`` the ones writing and reading
+datagrams (wire version 2): a per-stream stage budget and header on the way
+out, the header's stage count and a held record for lost hops on the way in.
 """
 import ctypes
 from dataclasses import dataclass
@@ -364,6 +367,118 @@ def rvq_lookup_wire_step(wire, codebook, codebooks, out, rows_per_sample=1, mean
     _count_operand("rvq_lookup_wire_step", n_active)
     L.call("sel_rvq_lookup_wire_step", L.ptr(wire), rows, rows_per_sample, S, K, D, L.ptr(codebook), L.ptr(mean),
            L.ptr(scale), L.ptr(n_active), CO._code(out.dtype), L.ptr(out), L.ptr(idx_out), L.stream())
+    return out
+
+
+# ---- the same with datagrams: stage budgets, headers, held records (include/sel.h, wire version 2) ----
+def _dgram_operand(what, dgram, B, S, K, T):
+    """(B, >= 4 + T * fb(S)) uint8 on the device, rows of one stride, bytes adjacent; any start address"""
+    from .wire import DatagramFormat
+    try:
+        need = DatagramFormat(S, K, T).stride
+    except ValueError as e:
+        raise L.SelError(f"sel: {what}: {e}") from None
+    if dgram is None or dgram.dtype != torch.uint8 or dgram.dim() != 2 or dgram.shape[0] != B \
+            or dgram.shape[1] < need or dgram.stride(1) != 1 or dgram.stride(0) < dgram.shape[1]:
+        raise L.SelError(f"sel: {what} takes a uint8 datagram buffer of shape ({B}, >= {need}), got "
+                         f"{None if dgram is None else (dgram.dtype, tuple(dgram.shape), dgram.stride())}")
+    return dgram.stride(0)
+
+
+def _control_operand(what, name, t, B):
+    if t is not None and (t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < B):
+        raise L.SelError(f"sel: {what} takes a contiguous int32 device tensor of {B} entries for {name}")
+
+
+def rvq_step_dgram(z, embeds, dgram, rows_per_sample=1, n_active=None, stages=None, seq=None, flatten=True, idx=None,
+                   zq=None):
+    """One sel_rvq_step_dgram launch on the current stream: rvq_step_wire whose
+    chain stops, per sample, after ``clamp(stages[i], 1, S)`` stages, writing a
+    datagram per sample -- the header {2, s_i, seq[i] as uint16} and the sample's
+    rows_per_sample records of s_i fields -- into the front of row i of dgram
+    (B, >= 4 + rows_per_sample * fb(S)) uint8.  stages / seq (B int32 each,
+    DEVICE; None: S / 0) are read by the kernel, so a captured launch follows what
+    is staged into them.  idx (optional) gets -1 in the stages not run, zq is the
+    truncated sum.  Nothing is allocated.  Returns dgram."""
+    L.need_device(z, embeds, dgram, idx, n_active, stages, seq, zq)
+    if embeds.dim() != 3 or embeds.dtype != torch.float32 or not embeds.is_contiguous():
+        raise L.SelError(f"sel: rvq_step_dgram takes a contiguous fp32 (S, D, K) stack, got {embeds.dtype} "
+                         f"{tuple(embeds.shape)}")
+    S, D, K = embeds.shape
+    if z.dim() != 2 or z.shape[1] != D or z.dtype != torch.float32 or not z.is_contiguous():
+        raise L.SelError(f"sel: rvq_step_dgram takes contiguous fp32 rows (rows, {D}), got {z.dtype} {tuple(z.shape)}")
+    rows = z.shape[0]
+    if idx is not None and (idx.dtype != torch.int64 or not idx.is_contiguous() or tuple(idx.shape) != (S, rows)):
+        raise L.SelError(f"sel: rvq_step_dgram writes a contiguous int64 idx of shape {(S, rows)}, got {idx.dtype} "
+                         f"{tuple(idx.shape)}")
+    if zq is not None and (zq.dtype != torch.float32 or not zq.is_contiguous() or zq.shape != z.shape):
+        raise L.SelError(f"sel: rvq_step_dgram writes a contiguous fp32 zq of shape {tuple(z.shape)}")
+    if rows_per_sample < 1 or rows % rows_per_sample:
+        raise L.SelError(f"sel: rvq_step_dgram rows ({rows}) is not a multiple of rows_per_sample ({rows_per_sample})")
+    B = rows // rows_per_sample
+    stride = _dgram_operand("rvq_step_dgram", dgram, B, S, K, rows_per_sample)
+    _count_operand("rvq_step_dgram", n_active)
+    _control_operand("rvq_step_dgram", "stages", stages, B)
+    _control_operand("rvq_step_dgram", "seq", seq, B)
+    L.call("sel_rvq_step_dgram", L.ptr(z), rows, rows_per_sample, D, L.ptr(embeds), S, K, L.ptr(n_active),
+           L.ptr(stages), L.ptr(seq), int(bool(flatten)), L.ptr(idx), L.ptr(zq), L.ptr(dgram), stride, L.stream())
+    return dgram
+
+
+def rvq_lookup_dgram_step(dgram, codebook, codebooks, out, rows_per_sample=1, mean=None, scale=None, n_active=None,
+                          slots=None, lost=None, hold=None, idx_out=None):
+    """One sel_rvq_lookup_dgram_step launch on the current stream: the lookup on
+    the records of the datagrams in dgram (B, >= 4 + rows_per_sample * fb(S))
+    uint8, each with the stage count its header gives, for a codebook (codebooks
+    * K, D) fp32 -> out (B * rows_per_sample, D) fp32 / bf16.  A sample whose
+    lost[i] is non-zero, or whose header is not {2, 1..S}, decodes in every row
+    the record that hold (nslots, >= 1 + fb(S)) uint8 keeps for its slot
+    (slots[i], None: i) from the last valid hop -- the empty sum when there is
+    none -- and a valid sample stores its last row's record there.  slots / lost:
+    B int32 each, DEVICE.  idx_out (codebooks, rows) int64, when given, receives
+    the ids summed.  Nothing is allocated.  Returns out."""
+    L.need_device(dgram, codebook, out, mean, scale, n_active, slots, lost, hold, idx_out)
+    if codebook.dim() != 2 or codebook.dtype != torch.float32 or not codebook.is_contiguous():
+        raise L.SelError(f"sel: rvq_lookup_dgram_step takes a contiguous fp32 (ncodes, D) codebook, got "
+                         f"{codebook.dtype} {tuple(codebook.shape)}")
+    ncodes, D = codebook.shape
+    S = int(codebooks)
+    if S < 1 or ncodes % S or ncodes < S:
+        raise L.SelError(f"sel: rvq_lookup_dgram_step: a codebook of {ncodes} rows is not {S} stages of one size")
+    K = ncodes // S
+    if rows_per_sample < 1:
+        raise L.SelError(f"sel: rvq_lookup_dgram_step rows_per_sample ({rows_per_sample}) must be positive")
+    if dgram is None or dgram.dim() != 2:
+        raise L.SelError("sel: rvq_lookup_dgram_step takes a (B, stride) uint8 datagram buffer")
+    B = dgram.shape[0]
+    rows = B * rows_per_sample
+    stride = _dgram_operand("rvq_lookup_dgram_step", dgram, B, S, K, rows_per_sample)
+    if out.dtype not in (torch.float32, torch.bfloat16) or not out.is_contiguous() or out.numel() != rows * D:
+        raise L.SelError(f"sel: rvq_lookup_dgram_step writes {rows} contiguous fp32 / bf16 rows of {D}, got "
+                         f"{out.dtype} {tuple(out.shape)}")
+    if idx_out is not None and (idx_out.dtype != torch.int64 or not idx_out.is_contiguous()
+                                or tuple(idx_out.shape) != (S, rows)):
+        raise L.SelError(f"sel: rvq_lookup_dgram_step writes a contiguous int64 idx_out of shape {(S, rows)}")
+    if (mean is None) != (scale is None):
+        raise L.SelError("sel: rvq_lookup_dgram_step takes mean and scale together or not at all")
+    for t in (mean, scale):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != D):
+            raise L.SelError(f"sel: rvq_lookup_dgram_step takes contiguous fp32 mean / scale of {D} elements")
+    nslots, hold_stride = 0, 0
+    if hold is not None:
+        from .wire import DatagramFormat
+        need = 1 + DatagramFormat(S, K).frame_bytes()
+        if hold.dtype != torch.uint8 or hold.dim() != 2 or hold.shape[0] < 1 or hold.shape[1] < need \
+                or hold.stride(1) != 1 or hold.stride(0) < hold.shape[1]:
+            raise L.SelError(f"sel: rvq_lookup_dgram_step takes uint8 hold rows of shape (nslots, >= {need}), got "
+                             f"{(hold.dtype, tuple(hold.shape), hold.stride())}")
+        nslots, hold_stride = hold.shape[0], hold.stride(0)
+    _count_operand("rvq_lookup_dgram_step", n_active)
+    _control_operand("rvq_lookup_dgram_step", "slots", slots, B)
+    _control_operand("rvq_lookup_dgram_step", "lost", lost, B)
+    L.call("sel_rvq_lookup_dgram_step", L.ptr(dgram), stride, rows, rows_per_sample, S, K, D, L.ptr(codebook),
+           L.ptr(mean), L.ptr(scale), L.ptr(n_active), L.ptr(slots), L.ptr(lost), L.ptr(hold), hold_stride, nslots,
+           CO._code(out.dtype), L.ptr(out), L.ptr(idx_out), L.stream())
     return out
 
 

@@ -47,7 +47,7 @@ class AudioDec(AudioCodec):
             return _load_generator(generator_hifigan, config, checkpoint)
         raise NotImplementedError(f"Decoder {config['model_type']} is not supported!")
 
-    def open_session(self, batch=1, chunk=300, graph=True, codes=False, wire=False):
+    def open_session(self, batch=1, chunk=300, graph=True, codes=False, wire=False, datagrams=False):
         """(tx, rx) streaming sessions, warmed up as load_transmitter / load_receiver
         left the models: ``tx.encode -> tx.quantize`` on the transmitter,
         ``rx.lookup -> rx.decode`` on the receiver.  The receiver's session runs
@@ -59,7 +59,10 @@ class AudioDec(AudioCodec):
         receiver knows rx_encoder): ``tx.transmit`` / ``rx.receive`` then run the
         quantizer and the lookup inside the hop.  ``wire=True`` (with ``codes``)
         makes that ``enable_codes(wire=True)``: ``tx.transmit_packets`` returns and
-        ``rx.receive_packets`` takes the bytes of the wire format (sel/wire.py)."""
+        ``rx.receive_packets`` takes the bytes of the wire format (sel/wire.py).
+        ``datagrams=True`` (with ``codes``) adds ``enable_codes(datagrams=True)``:
+        ``tx.transmit_datagrams(x, stages)`` / ``rx.receive_datagrams(p, lost)``,
+        datagrams with a header, a stage budget per stream and loss concealment."""
         from sel.streaming import StreamSession, VocoderSession
         if self.tx_encoder is None or self.rx_encoder is None or self.decoder is None:
             raise RuntimeError("open_session: call load_transmitter and load_receiver first")
@@ -77,17 +80,17 @@ class AudioDec(AudioCodec):
         rx.load_state()
         rx.lookup_generator = self.rx_encoder
         if codes:
-            tx.enable_codes(wire=wire)
-            rx.enable_codes(wire=wire)
+            tx.enable_codes(wire=wire, datagrams=datagrams)
+            rx.enable_codes(wire=wire, datagrams=datagrams)
         return tx, rx
 
-    def open_pool(self, capacity, chunk=300, graph=True, codes=False, wire=False):
+    def open_pool(self, capacity, chunk=300, graph=True, codes=False, wire=False, datagrams=False):
         """(tx_pool, rx_pool) for `capacity` independent streams, mirroring
         open_session: a ``StreamPool`` on the transmitter, a ``StreamPool`` or a
         ``VocoderPool`` (``chunk / hop`` frames per hop) on the receiver, both
         with the models' warmed-up pad_buffers as the template every newly
-        opened stream starts from.  ``codes=True`` and ``wire=True`` as in
-        ``open_session``."""
+        opened stream starts from.  ``codes=True``, ``wire=True`` and
+        ``datagrams=True`` as in ``open_session``."""
         from sel.streaming import StreamPool, VocoderPool
         if self.tx_encoder is None or self.rx_encoder is None or self.decoder is None:
             raise RuntimeError("open_pool: call load_transmitter and load_receiver first")
@@ -105,8 +108,8 @@ class AudioDec(AudioCodec):
         rx.load_state()
         rx.lookup_generator = self.rx_encoder
         if codes:
-            tx.enable_codes(wire=wire)
-            rx.enable_codes(wire=wire)
+            tx.enable_codes(wire=wire, datagrams=datagrams)
+            rx.enable_codes(wire=wire, datagrams=datagrams)
         return tx, rx
 
 

@@ -470,6 +470,71 @@ int sel_rvq_lookup_wire_step(const uint8_t* wire, int rows, int rows_per_sample,
                              const float* codebook, const float* mean, const float* scale, const int32_t* n_active,
                              int out_dtype, void* out, int64_t* idx_out, sel_stream_t stream);
 
+/* ---- the datagram, wire version 2 (csrc/vq_step.hip, sel/wire.py) ----
+ * What a sender puts on a network per hop and stream: a header and the hop's
+ * records truncated to the s <= S stages the sender chose (a residual VQ is a
+ * scalable code: the first s stages are a coarser code of the same frame).
+ *   byte 0      2                          the version
+ *   byte 1      s, 1 <= s <= S             stages carried by this datagram
+ *   bytes 2..3  seq, uint16 little-endian  the hop number of the stream, wrapping
+ *   bytes 4..   `frames` records: version 1's record with S replaced by s --
+ *               field j < s in bits [j*bits, (j+1)*bits), fb(s) = ceil(s*bits / 8)
+ *               bytes, pad bits written as zero and ignored on reading.
+ * A datagram is 4 + frames * fb(s) bytes; `frames` is not in the header (a
+ * receiver knows its own).  S <= 255.  S = 8, K = 1024: fb(1..8) = 2, 3, 4, 5, 7,
+ * 8, 9, 10.  A datagram buffer is (B, dgram_stride) uint8 with dgram_stride >=
+ * 4 + frames * fb(S): sample i owns [i*dgram_stride, (i+1)*dgram_stride), of
+ * which only the first 4 + frames * fb(s_i) bytes are written by the transmitter
+ * or read by the receiver.  No byte is shared between samples, nothing is
+ * atomic, byte accesses only: any start address and any stride.
+ *
+ * Both calls are single launches with their siblings' contract (no workspace,
+ * no allocation, no host synchronisation, capturable, SEL_ERR_ARG before any
+ * device work) and their active set: rows >= n * rows_per_sample are neither
+ * read nor written -- datagram bytes, idx, zq, out, idx_out and hold rows
+ * included.  stages, seq, slots and lost are DEVICE int32 arrays, dense in
+ * active order, one entry per sample i = row / rows_per_sample, so one captured
+ * launch serves every mix of budgets and losses staged into them.
+ *
+ * sel_rvq_step_dgram: s_i = clamp(stages[i], 1, S) (stages NULL: S; seq NULL: 0).
+ * A row's block runs sel_rvq_step's chain for stages 0 .. s_i - 1 and stops; the
+ * later codebooks are not requested.  Those picks are bit for bit the first s_i
+ * picks of sel_rvq_step on the row, zq is sel_rvq_step's with S = s_i on
+ * embeds[:s_i], idx[s, row] = -1 for s >= s_i (idx may be NULL).  The row's
+ * record of s_i fields goes to dgram + i*dgram_stride + 4 + r*fb(s_i), r = row %
+ * rows_per_sample; the block of the sample's first row writes the header, seq[i]
+ * as its low 16 bits.  Bytes beyond the datagram's length are not written.
+ * Accepted: what sel_rvq_step_wire accepts, S <= 255, dgram non-null,
+ * dgram_stride >= 4 + rows_per_sample * fb(S).
+ *
+ * sel_rvq_lookup_dgram_step: sample i is valid when lost is NULL or lost[i] == 0,
+ * byte 0 of its datagram is 2 and byte 1 is in [1, S]; a bad header makes the
+ * sample lost and nothing is read outside its region or the codebook.  slot =
+ * slots ? slots[i] : i; hold is (nslots, hold_stride) uint8, a row being {stages
+ * held (0: none), that record}.
+ *   valid: every row sums the fields of its own record as
+ *     sel_rvq_lookup_wire_step does (k >= K refused, pad bits ignored) -- bit for
+ *     bit sel_rvq_lookup_step on ids j*K + k_j for j < s_i and -1 beyond -- and
+ *     the sample's LAST row's record and s_i are copied into hold[slot];
+ *   lost: every row of the sample sums the record held by its slot, hold is not
+ *     written; nothing held (count 0, hold NULL, slot outside [0, nslots)) is
+ *     the empty sum, +0.0f per channel, then mean / scale.
+ * Within a launch a sample reads its hold row or writes it, never both; the
+ * slots of a launch must be distinct.  idx_out (S, rows), when non-null, receives
+ * the ids summed: the held ones on a lost hop, -1 for refused or absent fields.
+ * Accepted: what sel_rvq_lookup_wire_step accepts, S <= 255, the stride bound
+ * above, hold NULL or hold_stride >= 1 + fb(S) with nslots >= 1. */
+#define SEL_DGRAM_VERSION 2
+#define SEL_DGRAM_HEADER_BYTES 4
+int sel_rvq_step_dgram(const float* z, int rows, int rows_per_sample, int D, const float* embeds, int S, int K,
+                       const int32_t* n_active, const int32_t* stages, const int32_t* seq, int flatten,
+                       int64_t* idx, float* zq, uint8_t* dgram, int64_t dgram_stride, sel_stream_t stream);
+int sel_rvq_lookup_dgram_step(const uint8_t* dgram, int64_t dgram_stride, int rows, int rows_per_sample,
+                              int S, int K, int D, const float* codebook, const float* mean, const float* scale,
+                              const int32_t* n_active, const int32_t* slots, const int32_t* lost,
+                              uint8_t* hold, int64_t hold_stride, int nslots,
+                              int out_dtype, void* out, int64_t* idx_out, sel_stream_t stream);
+
 /* ---- residual VQ, training mode: the EMA codebook update, vq_module.py:74-80 ----
  * Runs after sel_rvq_fwd on the same x / embeds / idx / counts.  Training mode
  * changes nothing about the assignment (every stage picks its code with its own

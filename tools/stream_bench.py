@@ -69,8 +69,20 @@ plus, recorded only, the transmitter's hop with the result brought to the host
 (transmit + idx.cpu() against transmit_packets + .cpu()), and writes
 profiles/stream_wire_bench.{json,md} (the table of DESIGN §17).  Acceptance:
 every *_packets row no slower than the row beside it by the wider 5-95 % band.
+
+  python tools/stream_bench.py --datagrams
+measures datagrams (wire version 2, enable_codes(datagrams=True)), same protocol,
+the old path being an enable_codes(wire=True) object of the same kind:
+
+  transmit_packets  against  transmit_datagrams at s = S, and at s = 4, 2, 1
+  receive_packets   against  receive_datagrams with nothing lost, and with every stream lost
+
+and writes profiles/stream_dgram_bench.{json,md} (the table of DESIGN §20).
+Acceptance: the two s = S comparisons no slower by the wider 5-95 % band; the
+s < S rows are what a smaller stage budget saves.
 """
 import argparse
+import functools
 import json
 import os
 import sys
@@ -589,6 +601,94 @@ def main_wire(a, dev):
     print("\n".join(lines + verdicts))
 
 
+def run_dgram_config(kind, dtype, N, chunk, hops, warmup, dev):
+    """transmit_packets (the old path: an enable_codes(wire=True) object) against
+    transmit_datagrams at every stage budget in BUDGETS, receive_packets against
+    receive_datagrams with nothing lost, and a tick with every stream lost;
+    `kind` = "session" (batch N) or "pool" (N of N slots active), full width,
+    separate objects, the paths alternating hop by hop."""
+    from models.autoencoder.AudioDec import StreamGenerator as Encoder
+    from sel.streaming import StreamPool, StreamSession
+    torch.manual_seed(93)
+    E = Encoder().to(dev).eval()
+    E.quantizer.initial()
+    x = 0.1 * torch.randn(N, 1, chunk, generator=torch.Generator().manual_seed(1)).to(dev)
+    pool = kind == "pool"
+
+    def make(**kw):
+        o = StreamPool(E, N, chunk, graph=True, dtype=dtype) if pool else StreamSession(E, N, chunk, graph=True,
+                                                                                        dtype=dtype)
+        o.enable_codes(**kw)
+        return o, (([o.open() for _ in range(N)],) if pool else ())
+
+    S = len(E.quantizer.codebook.layers)
+    budgets = [S] + [b for b in (4, 2, 1) if b < S]
+    (tx_old, sl), (rx_old, _), (rx_new, _), (rx_lost, _) = (make(wire=True), make(wire=True), make(datagrams=True),
+                                                           make(datagrams=True))
+    tx_new = {b: make(datagrams=True)[0] for b in budgets}
+    packets = tx_old.transmit_packets(*sl, x).clone()
+    dgrams = tx_new[S].transmit_datagrams(*sl, x).clone()
+    gone = [1] * N
+    paths = {"tx": lambda: tx_old.transmit_packets(*sl, x), "rx": lambda: rx_old.receive_packets(*sl, packets),
+             "rx_dgram": lambda: rx_new.receive_datagrams(*sl, dgrams),
+             "rx_all_lost": lambda: rx_lost.receive_datagrams(*sl, dgrams, gone)}
+    for b in budgets:
+        paths[f"tx_dgram_s{b}"] = functools.partial(lambda o, b: o.transmit_datagrams(*sl, x, b), tx_new[b], b)
+    stream = torch.cuda.current_stream(dev)
+    rec = {p: dict(host=[], gpu=[]) for p in paths}
+    for hop in range(warmup + hops):
+        for p, fn in paths.items():
+            _, h, g = _timed(fn, stream)
+            if hop >= warmup:
+                rec[p]["host"].append(h)
+                rec[p]["gpu"].append(g)
+    f = rx_new.datagram
+    return dict(kind=kind, dtype=str(dtype).replace("torch.", ""), streams=N, chunk=chunk, hops=hops, budgets=budgets,
+                datagram=dict(version=f.version, bits=f.bits, stride=f.stride,
+                              bytes={b: f.datagram_bytes(b) for b in budgets},
+                              kbit_per_s={b: f.bitrate(48000, chunk, b) / 1e3 for b in budgets}),
+                paths={p: {k: _stats(v) for k, v in r.items()} for p, r in rec.items()})
+
+
+def main_dgram(a, dev):
+    results = []
+    for dt in a.dtypes:
+        for kind, N in (("session", 1), ("session", a.streams), ("pool", a.streams)):
+            r = run_dgram_config(kind, getattr(torch, dt), N, 300, a.hops, a.warmup, dev)
+            results.append(r)
+            print(json.dumps(r), flush=True)
+    S = results[0]["budgets"][0]
+    order = ["tx"] + [f"tx_dgram_s{b}" for b in results[0]["budgets"]] + ["rx", "rx_dgram", "rx_all_lost"]
+    label = {"tx": "transmit_packets", "rx": "receive_packets", "rx_dgram": "receive_datagrams, none lost",
+             "rx_all_lost": "receive_datagrams, all lost"}
+    label.update({f"tx_dgram_s{b}": f"transmit_datagrams s = {b}" for b in results[0]["budgets"]})
+    lines = ["| dtype | object | path | host ms med (p5-p95) | GPU ms med (p5-p95) |", "|---|---|---|---|---|"]
+    verdicts = []
+    for r in results:
+        what = f"{r['kind']} B={r['streams']}" if r["kind"] == "session" else f"pool {r['streams']} of {r['streams']}"
+        for p in order:
+            h, g = r["paths"][p]["host"], r["paths"][p]["gpu"]
+            lines.append(f"| {r['dtype']} | {what} | {label[p]} | {h['med']:.3f} ({h['p5']:.3f}-{h['p95']:.3f}) | "
+                         f"{g['med']:.3f} ({g['p5']:.3f}-{g['p95']:.3f}) |")
+        for old, new in (("tx", f"tx_dgram_s{S}"), ("rx", "rx_dgram")):
+            o, n = r["paths"][old]["host"], r["paths"][new]["host"]
+            gain = o["med"] - n["med"]
+            spread = max(o["p95"] - o["p5"], n["p95"] - n["p5"])
+            verdicts.append(f"acceptance {r['dtype']} {what} {label[new]} against {label[old]} (no slower): old "
+                            f"{o['med']:.3f} ms - new {n['med']:.3f} ms = {gain:.3f} ms vs 5-95% band {spread:.3f} ms: "
+                            f"{'MET' if gain >= -spread else 'NOT MET'}")
+    d = results[0]["datagram"]
+    verdicts.append(f"datagram v{d['version']}: {d['bits']} bits per field, bytes per hop by budget {d['bytes']}, "
+                    f"kbit/s at chunk 300 with the header {d['kbit_per_s']}")
+    out = a.out or os.path.join(REPO, "profiles", "stream_dgram_bench")
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out + ".json", "w") as f:
+        json.dump(results, f, indent=1)
+    with open(out + ".md", "w") as f:
+        f.write("\n".join(lines + [""] + verdicts) + "\n")
+    print("\n".join(lines + verdicts))
+
+
 def main_vocoder(a, dev):
     results = []
     for dec in a.decoder:
@@ -648,6 +748,10 @@ def main():
     ap.add_argument("--wire", action="store_true",
                     help="the packets of the wire format inside the hop graphs: transmit against transmit_packets, "
                          "receive against receive_packets (profiles/stream_wire_bench)")
+    ap.add_argument("--datagrams", action="store_true",
+                    help="datagrams inside the hop graphs: transmit_packets against transmit_datagrams at stage "
+                         "budgets S, 4, 2, 1, receive_packets against receive_datagrams, and a tick with every "
+                         "stream lost (profiles/stream_dgram_bench)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -659,6 +763,8 @@ def main():
         return main_codes(a, dev)
     if a.wire:
         return main_wire(a, dev)
+    if a.datagrams:
+        return main_dgram(a, dev)
     if a.pool:
         return main_attribution(a, dev) if a.attribution else main_pool(a, dev)
     if a.decoder != ["audiodec"]:
