@@ -38,6 +38,18 @@ version 2, ``sel.wire.DatagramFormat``): ``transmit_datagrams`` stops the
 quantizer after each stream's stage budget and writes a header with the stage
 count and the hop number; ``receive_datagrams`` decodes whatever stage count
 arrives and conceals a hop that did not, from the stream's last good record.
+
+Inside, all of these are one mechanism.  A ``_Half`` holds the fixed buffers
+and the step launches of ``encode`` or ``decode``, and a dict of named hop
+variants (``_Hop``): the plain hop, and whatever ``enable_codes`` added with
+``add_hop(name, pre=..., post=..., **buffers)`` -- "codes", "wire", "dgram" --
+each a launch list ``pre -> steps -> commit -> post`` with its own graph and
+the buffers it owns; ``run(name)`` replays one.  The six ``transmit*`` /
+``receive*`` methods are written once, in ``_CodesMixin``, for sessions
+(``method(x)``) and pools (``method(slots, x)``); what differs between the two --
+the slot list to stage, n of capacity rows, the wording of errors, how a
+datagram hop's control words reach the device -- is a handful of hooks, the
+session's in ``_CodesMixin``, the pool's in ``_PoolBase``.
 """
 import functools
 
@@ -49,25 +61,47 @@ from . import streamops as SO
 from .wire import WireFormat
 
 
+class _Hop:
+    """One named variant of a half's hop: ``pre -> steps -> commit -> post`` as a
+    launch list and, for a captured half, a graph of its own.  ``pre`` / ``post``
+    are stateless launches in front of the steps (a lookup into ``inp``) or behind
+    them (a quantizer on ``outs[-1]``); the plain hop has neither.  Beside them
+    the fixed buffers the variant owns -- ``idx`` (S, rows) code indices, ``buf``
+    packets (rows, frame_bytes) or datagrams (streams, stride), ``ctl`` the device
+    control words a datagram launch reads (staged before every replay), ``hold``
+    the receiver's held records -- and the views of them a per-hop method hands
+    out, prepared once: ``idx_out`` (S, streams, frames), ``packets`` (streams,
+    packet_bytes), ``y`` (streams, out_channels, samples) of the half's output.
+    ``staged``: on a session, the control words the device holds (None: unknown)."""
+
+    def __init__(self, pre=None, post=None, idx=None, buf=None, ctl=None, hold=None, idx_out=None, packets=None,
+                 y=None):
+        self.pre, self.post, self.graph, self.staged = pre, post, None, None
+        self.idx, self.buf, self.ctl, self.hold = idx, buf, ctl, hold
+        self.idx_out, self.packets, self.y = idx_out, packets, y
+
+
 class _Half:
     """The launches of one method (encode or decode) on fixed buffers."""
+    _step = staticmethod(SO.conv_step)
 
     def __init__(self, steps, generator, batch, in_channels, dtype, device):
-        params = dict(generator.named_parameters())
         self.steps = steps
         self.batch = batch
         T0 = steps[0].T * (steps[0].stride if steps[0].kind == CO.PACK_FWD_STRIDED else 1)
         self.inp = torch.zeros((batch, T0, in_channels), dtype=dtype, device=device)
         self.descs, self.wps, self.biases, self.outs = [], [], [], []
         self.carry, self.carry_out = [], []
-        for st in steps:
-            w = params[st.weight]
-            L.need_device(w)
+        for i, st in enumerate(steps):
+            wp, bias = self._weights(generator, st, dtype)
             self.descs.append(st.desc(batch))
-            self.wps.append(CO.PACKS.get(st.kind, w, st.stride, dtype)[0])
-            self.biases.append(params[st.bias].detach().float().contiguous() if st.bias else None)
-            self.outs.append(torch.zeros((batch * st.T, st.N), dtype=torch.float32 if st.out_float else dtype,
-                                         device=device))
+            self.wps.append(wp)
+            self.biases.append(bias)
+            if getattr(st, "out", i) != i:
+                self.outs.append(self.outs[st.out])    # a vocoder step that accumulates into an earlier one's buffer
+            else:
+                self.outs.append(torch.zeros((batch * st.T, st.N), dtype=torch.float32 if st.out_float else dtype,
+                                             device=device))
             if st.carry_shape is None:
                 self.carry.append(None)
                 self.carry_out.append(None)
@@ -75,16 +109,42 @@ class _Half:
                 self.carry.append(torch.zeros(st.carry_shape, dtype=dtype, device=device))
                 self.carry_out.append(torch.zeros(st.carry_shape, dtype=dtype, device=device))
         self.pairs = [(o, c) for o, c in zip(self.carry_out, self.carry) if c is not None]
-        self.graph = None
+        self.hops = {None: _Hop()}         # the variants by name; None: the plain hop
+
+    @staticmethod
+    def _weights(generator, st, dtype):
+        """(packed weight, fp32 bias or None) of a step"""
+        w = generator.get_parameter(st.weight)
+        L.need_device(w)
+        bias = generator.get_parameter(st.bias).detach().float().contiguous() if st.bias else None
+        return CO.PACKS.get(st.kind, w, st.stride, dtype)[0], bias
+
+    @property
+    def graph(self):
+        return self.hops[None].graph
+
+    @property
+    def hold(self):
+        """the receiver's held records once enable_codes(datagrams=True) ran"""
+        hop = self.hops.get("dgram")
+        return None if hop is None else hop.hold
 
     def _buf(self, i):
         return self.inp if i == -1 else self.outs[i]
 
-    def launch(self):
+    def _launch_steps(self):
+        step = self._step
         for i, st in enumerate(self.steps):
-            SO.conv_step(self.descs[i], self.carry[i], self._buf(st.src), self.wps[i], self.biases[i],
-                         None if st.res is None else self._buf(st.res), self.outs[i], self.carry_out[i])
+            step(self.descs[i], self.carry[i], self._buf(st.src), self.wps[i], self.biases[i],
+                 None if st.res is None else self._buf(st.res), self.outs[i], self.carry_out[i])
         SO.commit(self.pairs)
+
+    def launch(self, hop=None):
+        if hop is not None and hop.pre is not None:
+            hop.pre()
+        self._launch_steps()
+        if hop is not None and hop.post is not None:
+            hop.post()
 
     def capture(self, warmup=2):
         dev = self.inp.device
@@ -96,15 +156,37 @@ class _Half:
                 self.launch()
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
             self.launch()
+        self.hops[None].graph = graph
 
-    def run(self):
+    def add_hop(self, name, pre=None, post=None, **buffers):
+        """A further variant of the hop beside the plain one: a second launch list
+        with a stateless launch in front of the steps (``pre``) or behind them
+        (``post``) and, for a captured half, a second graph.  Only the new launch is
+        warmed up eagerly (it has no state; a pool's runs with ``n_active = 0``); the
+        capture itself executes nothing, so no carry moves.  ``buffers``: the fixed
+        tensors the variant owns (_Hop)."""
+        hop = self.hops[name] = _Hop(pre, post, **buffers)
         if self.graph is not None:
-            self.graph.replay()
+            (pre or post)()
+            torch.cuda.synchronize(self.inp.device)
+            hop.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(hop.graph):
+                self.launch(hop)
+        return hop
+
+    def drop_hops(self):
+        self.hops = {None: self.hops[None]}
+
+    def run(self, name=None):
+        """Replay the variant's graph, or issue its launch list."""
+        hop = self.hops[name]
+        if hop.graph is not None:
+            hop.graph.replay()
         else:
-            self.launch()
+            self.launch(hop)
         return self.outs[-1]
 
     def zero(self):
@@ -112,107 +194,22 @@ class _Half:
             if c is not None:
                 c.zero_()
 
-    # ---- code indices inside the hop (enable_codes) --------------------------------
-    pre = post = codes_graph = idx = None
-    pre_wire = wire_graph = wire_buf = None
 
-    def add_codes(self, idx, pre=None, post=None, wire_buf=None, pre_wire=None):
-        """Extend the hop by a stateless launch in front of it (``pre``: the lookup
-        into ``inp``) or behind it (``post``: the quantizer on ``outs[-1]``), as a
-        second launch list beside ``launch`` -- and, for a captured half, a second
-        graph beside ``graph``.  Only the new launch is warmed up eagerly (it has
-        no state); the capture itself executes nothing, so no carry moves.
-        ``wire_buf``: the fixed (rows, frame_bytes) packet buffer -- ``post`` then
-        writes it beside ``idx``; ``pre_wire``, the lookup out of it, heads a third
-        launch list (and graph) beside ``pre``'s."""
-        self.idx, self.pre, self.post = idx, pre, post
-        self.wire_buf, self.pre_wire = wire_buf, pre_wire
-        self.codes_graph = self.wire_graph = None
-        if self.graph is not None:
-            (pre or post)()
-            if pre_wire is not None:
-                pre_wire()
-            torch.cuda.synchronize(self.inp.device)
-            self.codes_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.codes_graph):
-                self.launch_codes(self.pre)
-            if pre_wire is not None:
-                self.wire_graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.wire_graph):
-                    self.launch_codes(self.pre_wire)
-
-    def launch_codes(self, pre):
-        if pre is not None:
-            pre()
-        self.launch()
-        if self.post is not None:
-            self.post()
-
-    def run_codes(self):
-        if self.codes_graph is not None:
-            self.codes_graph.replay()
-        else:
-            self.launch_codes(self.pre)
-        return self.outs[-1]
-
-    def run_wire(self):
-        """The receiver's hop from the packet buffer: lookup_wire_step -> steps -> commit."""
-        if self.wire_graph is not None:
-            self.wire_graph.replay()
-        else:
-            self.launch_codes(self.pre_wire)
-        return self.outs[-1]
-
-    # ---- datagrams inside the hop (enable_codes(datagrams=True)) ---------------------
-    pre_dgram = post_dgram = dgram_graph = dgram_buf = dgram_ctl = hold = None
-    dgram_staged = None       # sessions: the control words the device holds (None: unknown)
-
-    def add_datagrams(self, buf, ctl, pre=None, post=None, hold=None):
-        """A further launch list beside the others, ``pre -> steps -> commit`` (the
-        receiver: lookup_dgram_step out of ``buf``) or ``steps -> commit -> post``
-        (the transmitter: rvq_step_dgram into ``buf``), and for a captured half a
-        further graph.  ``ctl``: the device control words the new launch reads
-        (budgets and hop numbers, or loss flags), staged before every replay.
-        ``hold``: the receiver's per-stream held records.  As in ``add_codes`` only
-        the new stateless launch is warmed up and the capture executes nothing."""
-        self.dgram_buf, self.dgram_ctl, self.pre_dgram, self.post_dgram, self.hold = buf, ctl, pre, post, hold
-        self.dgram_graph = self.dgram_staged = None
-        if self.graph is not None:
-            (pre or post)()
-            torch.cuda.synchronize(self.inp.device)
-            self.dgram_graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.dgram_graph):
-                self.launch_dgram()
-
-    def launch_dgram(self):
-        if self.pre_dgram is not None:
-            self.pre_dgram()
-        self.launch()
-        if self.post_dgram is not None:
-            self.post_dgram()
-
-    def run_dgram(self):
-        if self.dgram_graph is not None:
-            self.dgram_graph.replay()
-        else:
-            self.launch_dgram()
-        return self.outs[-1]
-
-
-def _fill_idx(dst, idx, what):
-    """idx (S, [batch,] frames) int64 -> the fixed (S, rows) buffer (or its first rows)."""
+def _fill_idx(dst, idx, owner, which, n):
+    """idx (S, [batch,] frames) int64 -> the fixed (S, rows) buffer (or its first rows); owner._what(which, n)
+    names the call when it is refused."""
     L.need_device(idx)
     if idx.dtype != torch.int64 or idx.dim() < 2 or idx.shape[0] != dst.shape[0] or idx.numel() != dst.numel():
-        raise L.SelError(f"sel: {what} takes int64 indices of {dst.shape[0]} codebooks x {dst.shape[1]} frames, "
+        raise L.SelError(f"sel: {owner._what(which, n)} takes int64 indices of {dst.shape[0]} codebooks x {dst.shape[1]} frames, "
                          f"got {idx.dtype} {tuple(idx.shape)}")
     dst.copy_(idx.reshape(dst.shape))
 
 
-def _fill_packets(dst, p, what):
+def _fill_packets(dst, p, owner, which, n):
     """p (n, packet_bytes) uint8 -> the fixed packet buffer (or its first n packets)."""
     L.need_device(p)
     if p.dtype != torch.uint8 or tuple(p.shape) != tuple(dst.shape):
-        raise L.SelError(f"sel: {what} takes uint8 packets of shape {tuple(dst.shape)}, got {p.dtype} {tuple(p.shape)}")
+        raise L.SelError(f"sel: {owner._what(which, n)} takes uint8 packets of shape {tuple(dst.shape)}, got {p.dtype} {tuple(p.shape)}")
     dst.copy_(p)
 
 
@@ -259,97 +256,118 @@ class _CodesMixin:
         conceals a hop that did not arrive by repeating the stream's last good
         record (``receive_datagrams``).  Budgets, hop numbers and loss flags are
         device words staged before the replay, so one graph serves every mix."""
-        dev = self._dec.inp.device
-        frames = self.plan.frames
+        for half in self._halves:
+            half.drop_hops()
         self._tx = self._rx = self.wire = self.datagram = None
         self._seq = self._dstats = None
-        self._dgram_enabled = False
-        fmt, dfmt = [], []
-        enc = getattr(self, "_enc", None)
-        if enc is not None and self.plan.pqc:
-            rvq = self.generator.quantizer.codebook
-            stack = torch.stack([l.embed.detach() for l in rvq.layers]).to(dev, torch.float32).contiguous().clone()
-            z = enc.outs[-1]
-            if z.dtype != torch.float32 or z.shape[1] != stack.shape[1]:
-                raise L.SelError(f"sel: encode's output rows {z.dtype} {tuple(z.shape)} are not the fp32 code vectors "
-                                 f"of a (S, D, K) = {tuple(stack.shape)} quantizer")
-            idx = torch.zeros((stack.shape[0], z.shape[0]), dtype=torch.int64, device=dev)
-            count = getattr(enc, "n_active", None)
-            self._prepare_codes(enc)
-            if wire:
-                fmt.append(WireFormat(stack.shape[0], stack.shape[2], frames))
-                buf = torch.zeros((z.shape[0], fmt[-1].frame_bytes), dtype=torch.uint8, device=dev)
-                enc.add_codes(idx, post=functools.partial(SO.rvq_step_wire, z, stack, buf, frames, count, True, idx),
-                              wire_buf=buf)
-            else:
-                enc.add_codes(idx, post=functools.partial(SO.rvq_step, z, stack, idx, frames, count, True))
-            if datagrams:
-                dfmt.append(self._datagram_format(stack.shape[0], stack.shape[2], frames))
-                B = z.shape[0] // frames
-                dbuf = torch.zeros((B, dfmt[-1].stride), dtype=torch.uint8, device=dev)
-                ctl, (stages, seq) = self._dgram_words(enc, B, 2, dev)
-                post = functools.partial(SO.rvq_step_dgram, z, stack, dbuf, frames, count, stages, seq, True)
-                if count is None:
-                    # a session (no slot list to stage): the hop numbers advance on the device, behind
-                    # the launch that read them, so a steady budget needs no control copy per hop
-                    def post(launch=post, seq=seq):
-                        launch()
-                        seq.add_(1)
-                enc.add_datagrams(dbuf, ctl, post=post)
-            self._tx = enc
-        lg = lookup_generator if lookup_generator is not None else self.lookup_generator
-        dec = self._dec
-        if lg is not None and (enc is None or self.plan.pqc):
-            rvq = lg.quantizer.codebook
-            if not hasattr(rvq, "codebook_size"):
-                lg.quantizer.initial()
-            flat = rvq.codebook.detach().to(dev, torch.float32).contiguous().clone()
-            S = len(rvq.layers)
-            if dec.inp.shape[-1] != flat.shape[1]:
-                raise L.SelError(f"sel: the lookup codebook has {flat.shape[1]} channels, decode takes "
-                                 f"{dec.inp.shape[-1]}")
-            idx = torch.zeros((S, dec.inp.shape[0] * frames), dtype=torch.int64, device=dev)
-            mean = scale = None
-            if getattr(self.generator, "norm", False):
-                mean = self.generator.mean.detach().to(dev, torch.float32).contiguous().clone()
-                scale = self.generator.scale.detach().to(dev, torch.float32).contiguous().clone()
-            count = getattr(dec, "n_active", None)
-            self._prepare_codes(dec)
-            pre = functools.partial(SO.rvq_lookup_step, idx, flat, dec.inp, frames, mean, scale, count)
-            if wire:
-                if flat.shape[0] % S:
-                    raise L.SelError(f"sel: the lookup codebook's {flat.shape[0]} rows are not {S} stages of one size")
-                fmt.append(WireFormat(S, flat.shape[0] // S, frames))
-                buf = torch.zeros((idx.shape[1], fmt[-1].frame_bytes), dtype=torch.uint8, device=dev)
-                dec.add_codes(idx, pre=pre, wire_buf=buf,
-                              pre_wire=functools.partial(SO.rvq_lookup_wire_step, buf, flat, S, dec.inp, frames, mean,
-                                                         scale, count))
-            else:
-                dec.add_codes(idx, pre=pre)
-            if datagrams:
-                if flat.shape[0] % S:
-                    raise L.SelError(f"sel: the lookup codebook's {flat.shape[0]} rows are not {S} stages of one size")
-                dfmt.append(self._datagram_format(S, flat.shape[0] // S, frames))
-                B = dec.inp.shape[0]
-                dbuf = torch.zeros((B, dfmt[-1].stride), dtype=torch.uint8, device=dev)
-                # a stream's last good record, at a fixed address: one row per batch stream / pool slot
-                hold = torch.zeros((B, 1 + dfmt[-1].frame_bytes()), dtype=torch.uint8, device=dev)
-                ctl, (lost,) = self._dgram_words(dec, B, 1, dev)
-                dec.add_datagrams(dbuf, ctl, hold=hold,
-                                  pre=functools.partial(SO.rvq_lookup_dgram_step, dbuf, flat, S, dec.inp, frames, mean,
-                                                        scale, count, getattr(dec, "slots", None), lost, hold))
-            self._rx = dec
-        for f in (fmt, dfmt):
-            if len(f) == 2 and (f[0].codebooks, f[0].codebook_size) != (f[1].codebooks, f[1].codebook_size):
-                raise L.SelError(f"sel: the transmitter packs {f[0]!r}, the lookup codebook reads {f[1]!r}")
-        if fmt:
-            self.wire = fmt[0]
-        if dfmt:
-            self.datagram = dfmt[0]
+        self._all = range(self._dec.inp.shape[0])        # a session's streams
+        self._codes_enabled = self._wire_enabled = self._dgram_enabled = False
+        tx = self._build_transmitter(wire, datagrams)
+        rx = self._build_receiver(lookup_generator if lookup_generator is not None else self.lookup_generator, wire,
+                                  datagrams)
+        for name in ("wire", "dgram"):
+            if name in tx and name in rx and (tx[name].codebooks, tx[name].codebook_size) != (rx[name].codebooks,
+                                                                                              rx[name].codebook_size):
+                raise L.SelError(f"sel: the transmitter packs {tx[name]!r}, the lookup codebook reads {rx[name]!r}")
+        fmt = {**rx, **tx}
+        self.wire, self.datagram = fmt.get("wire"), fmt.get("dgram")
+        if self.datagram is not None:
             streams = self._dec.inp.shape[0]
             self._seq = [0] * streams
             self._dstats = [self._new_stats() for _ in range(streams)]
         self._codes_enabled, self._wire_enabled, self._dgram_enabled = True, bool(wire), bool(datagrams)
+
+    def _build_transmitter(self, wire, datagrams):
+        """The variants of the transmitter half (an AudioDec session / pool with PQC):
+        "codes", whose quantizer launch writes the indices and, with ``wire``, the
+        packets beside them -- ``transmit`` and ``transmit_packets`` are the same
+        replay -- and "dgram".  -> {"wire" / "dgram": the format built}."""
+        enc = getattr(self, "_enc", None)
+        if enc is None or not self.plan.pqc:
+            return {}
+        dev, frames, fmt = enc.inp.device, self.plan.frames, {}
+        rvq = self.generator.quantizer.codebook
+        stack = torch.stack([l.embed.detach() for l in rvq.layers]).to(dev, torch.float32).contiguous().clone()
+        z = enc.outs[-1]
+        if z.dtype != torch.float32 or z.shape[1] != stack.shape[1]:
+            raise L.SelError(f"sel: encode's output rows {z.dtype} {tuple(z.shape)} are not the fp32 code vectors "
+                             f"of a (S, D, K) = {tuple(stack.shape)} quantizer")
+        S, K = stack.shape[0], stack.shape[2]
+        idx = torch.zeros((S, z.shape[0]), dtype=torch.int64, device=dev)
+        idx_out = self._idx_view(idx.view(S, -1, frames))
+        count = getattr(enc, "n_active", None)
+        self._prepare_codes(enc)
+        if wire:
+            fmt["wire"] = WireFormat(S, K, frames)
+            buf = torch.zeros((z.shape[0], fmt["wire"].frame_bytes), dtype=torch.uint8, device=dev)
+            enc.add_hop("codes", post=functools.partial(SO.rvq_step_wire, z, stack, buf, frames, count, True, idx),
+                        idx=idx, idx_out=idx_out, buf=buf, packets=buf.view(-1, fmt["wire"].packet_bytes))
+        else:
+            enc.add_hop("codes", post=functools.partial(SO.rvq_step, z, stack, idx, frames, count, True), idx=idx,
+                        idx_out=idx_out)
+        if datagrams:
+            fmt["dgram"] = self._datagram_format(S, K, frames)
+            B = z.shape[0] // frames
+            dbuf = torch.zeros((B, fmt["dgram"].stride), dtype=torch.uint8, device=dev)
+            ctl, (stages, seq) = self._dgram_words(enc, B, 2, dev)
+            post = functools.partial(SO.rvq_step_dgram, z, stack, dbuf, frames, count, stages, seq, True)
+            if count is None:
+                # a session (no slot list to stage): the hop numbers advance on the device, behind
+                # the launch that read them, so a steady budget needs no control copy per hop
+                def post(launch=post, seq=seq):
+                    launch()
+                    seq.add_(1)
+            enc.add_hop("dgram", post=post, buf=dbuf, ctl=ctl)
+        self._tx = enc
+        return fmt
+
+    def _build_receiver(self, lg, wire, datagrams):
+        """The variants of the receiver half for the flat (S*K, D) codebook of ``lg``
+        (none: no receiver half): "codes", the lookup out of the index buffer,
+        "wire", a list and graph of its own that looks the codes up straight out of
+        the packet buffer, and "dgram".  -> {"wire" / "dgram": the format built}."""
+        dec = self._dec
+        if lg is None or (getattr(self, "_enc", None) is not None and not self.plan.pqc):
+            return {}
+        dev, frames, fmt = dec.inp.device, self.plan.frames, {}
+        rvq = lg.quantizer.codebook
+        if not hasattr(rvq, "codebook_size"):
+            lg.quantizer.initial()
+        flat = rvq.codebook.detach().to(dev, torch.float32).contiguous().clone()
+        S = len(rvq.layers)
+        if dec.inp.shape[-1] != flat.shape[1]:
+            raise L.SelError(f"sel: the lookup codebook has {flat.shape[1]} channels, decode takes "
+                             f"{dec.inp.shape[-1]}")
+        B = dec.inp.shape[0]
+        idx = torch.zeros((S, B * frames), dtype=torch.int64, device=dev)
+        y = dec.outs[-1].view(B, self.plan.out_samples, self.plan.out_channels).transpose(1, 2)
+        mean = scale = None
+        if getattr(self.generator, "norm", False):
+            mean = self.generator.mean.detach().to(dev, torch.float32).contiguous().clone()
+            scale = self.generator.scale.detach().to(dev, torch.float32).contiguous().clone()
+        if (wire or datagrams) and flat.shape[0] % S:
+            raise L.SelError(f"sel: the lookup codebook's {flat.shape[0]} rows are not {S} stages of one size")
+        count = getattr(dec, "n_active", None)
+        self._prepare_codes(dec)
+        dec.add_hop("codes", pre=functools.partial(SO.rvq_lookup_step, idx, flat, dec.inp, frames, mean, scale, count),
+                    idx=idx, y=y)
+        if wire:
+            fmt["wire"] = WireFormat(S, flat.shape[0] // S, frames)
+            buf = torch.zeros((idx.shape[1], fmt["wire"].frame_bytes), dtype=torch.uint8, device=dev)
+            dec.add_hop("wire", pre=functools.partial(SO.rvq_lookup_wire_step, buf, flat, S, dec.inp, frames, mean,
+                                                      scale, count),
+                        buf=buf, packets=buf.view(B, fmt["wire"].packet_bytes), y=y)
+        if datagrams:
+            fmt["dgram"] = self._datagram_format(S, flat.shape[0] // S, frames)
+            dbuf = torch.zeros((B, fmt["dgram"].stride), dtype=torch.uint8, device=dev)
+            # a stream's last good record, at a fixed address: one row per batch stream / pool slot
+            hold = torch.zeros((B, 1 + fmt["dgram"].frame_bytes()), dtype=torch.uint8, device=dev)
+            ctl, (lost,) = self._dgram_words(dec, B, 1, dev)
+            dec.add_hop("dgram", pre=functools.partial(SO.rvq_lookup_dgram_step, dbuf, flat, S, dec.inp, frames, mean,
+                                                       scale, count, getattr(dec, "slots", None), lost, hold),
+                        buf=dbuf, ctl=ctl, hold=hold, y=y)
+        self._rx = dec
+        return fmt
 
     # ---- datagrams: formats, control words, counters ----------------------------------------
     @staticmethod
@@ -382,26 +400,26 @@ class _CodesMixin:
         if self._rx is not None and self._rx.hold is not None:
             self._rx.hold[i].zero_()
 
-    def _stage_list(self, what, stages, n):
+    def _stage_list(self, which, stages, n):
         """``stages``: None (all), an int, or one int per stream, each in [1, S] -> a list of n ints."""
         S = self.datagram.codebooks
         if stages is None:
             return [S] * n
         if isinstance(stages, torch.Tensor):
             if stages.dim() > 1 or stages.dtype not in (torch.int32, torch.int64):
-                raise L.SelError(f"sel: {what} takes stages as an int or {n} ints, got {stages.dtype} "
+                raise L.SelError(f"sel: {self._what(which, n)} takes stages as an int or {n} ints, got {stages.dtype} "
                                  f"{tuple(stages.shape)}")
             stages = stages.tolist()
         raw = [stages] * n if isinstance(stages, int) and not isinstance(stages, bool) else list(stages) \
             if isinstance(stages, (list, tuple)) else None
         if raw is None or len(raw) != n:
-            raise L.SelError(f"sel: {what} takes stages as an int or {n} ints, got {stages!r}")
+            raise L.SelError(f"sel: {self._what(which, n)} takes stages as an int or {n} ints, got {stages!r}")
         for s in raw:
             if not isinstance(s, int) or isinstance(s, bool) or not 1 <= s <= S:
-                raise L.SelError(f"sel: {what}: a budget of {s!r} stages, the quantizer has 1..{S}")
+                raise L.SelError(f"sel: {self._what(which, n)}: a budget of {s!r} stages, the quantizer has 1..{S}")
         return raw
 
-    def _take_datagrams(self, what, dst, p, lost, streams):
+    def _take_datagrams(self, which, dst, p, lost, streams):
         """Fill the fixed buffer's rows ``dst`` (n, stride) from ``p`` and return the n
         loss flags, counting per stream.  ``p``: a device uint8 (n, stride) tensor
         (``lost``: n flags or None), or a list of bytes-like / None entries, which
@@ -412,19 +430,19 @@ class _CodesMixin:
         if isinstance(p, torch.Tensor):
             L.need_device(p)
             if p.dtype != torch.uint8 or tuple(p.shape) != tuple(dst.shape):
-                raise L.SelError(f"sel: {what} takes uint8 datagrams of shape {tuple(dst.shape)}, got {p.dtype} "
+                raise L.SelError(f"sel: {self._what(which, n)} takes uint8 datagrams of shape {tuple(dst.shape)}, got {p.dtype} "
                                  f"{tuple(p.shape)}")
-            flags = self._flag_list(what, lost, n)
+            flags = self._flag_list(which, lost, n)
             dst.copy_(p)
         elif isinstance(p, (list, tuple)):
             if len(p) != n or any(d is not None and not isinstance(d, (bytes, bytearray, memoryview)) for d in p):
-                raise L.SelError(f"sel: {what} takes {n} datagrams, each bytes-like or None")
+                raise L.SelError(f"sel: {self._what(which, n)} takes {n} datagrams, each bytes-like or None")
             buf, gone, refused = fmt.assemble(p)
-            flags = [int(a or b) for a, b in zip(gone, self._flag_list(what, lost, n))]
+            flags = [int(a or b) for a, b in zip(gone, self._flag_list(which, lost, n))]
             heads = [None if f else fmt.parse(d) for f, d in zip(gone, p)]
             dst.copy_(buf)
         else:
-            raise L.SelError(f"sel: {what} takes a device uint8 tensor or a list of bytes-like / None entries, got "
+            raise L.SelError(f"sel: {self._what(which, n)} takes a device uint8 tensor or a list of bytes-like / None entries, got "
                              f"{type(p).__name__}")
         for j, (i, f) in enumerate(zip(streams, flags)):
             st = self._dstats[i]
@@ -442,17 +460,16 @@ class _CodesMixin:
                 st["stages"], st["seq"] = s, q
         return flags
 
-    @staticmethod
-    def _flag_list(what, lost, n):
+    def _flag_list(self, which, lost, n):
         if lost is None:
             return [0] * n
         if isinstance(lost, torch.Tensor):
             if lost.dim() != 1 or lost.dtype not in (torch.bool, torch.int32, torch.int64):
-                raise L.SelError(f"sel: {what} takes lost as {n} flags, got {lost.dtype} {tuple(lost.shape)}")
+                raise L.SelError(f"sel: {self._what(which, n)} takes lost as {n} flags, got {lost.dtype} {tuple(lost.shape)}")
             lost = lost.tolist()
         if not isinstance(lost, (list, tuple)) or len(lost) != n or \
                 any(not isinstance(f, (bool, int)) for f in lost):
-            raise L.SelError(f"sel: {what} takes lost as {n} flags, got {lost!r}")
+            raise L.SelError(f"sel: {self._what(which, n)} takes lost as {n} flags, got {lost!r}")
         return [int(bool(f)) for f in lost]
 
     def _prepare_codes(self, half):
@@ -475,8 +492,265 @@ class _CodesMixin:
                              "codebooks decode the indices) and call enable_codes() again")
         return self._rx
 
+    # ---- what differs between a session and a pool, as hooks (the pool's: _PoolBase) -----------
+    # A per-hop method takes (x) on a session and (slots, x) on a pool.  _begin splits that into
+    # (slots, x, optional); a session's slots are None, and so is its n below: every stream, the
+    # whole of each fixed buffer, nothing to stage.  A pool's n counts the listed slots.
+    def _begin(self, which, args, opt=None, takes_opt=False):
+        if len(args) != 1:
+            opt = self._optional(which, args, 1, opt, takes_opt)
+        return None, args[0], opt
 
-class StreamSession(_CodesMixin):
+    @staticmethod
+    def _optional(which, args, lead, opt, takes_opt):
+        """the datagram methods' optional argument given by position, or a TypeError for the arity"""
+        if len(args) != lead + 1 or not takes_opt or opt is not None:
+            raise TypeError(f"{which}() takes {'a slot list and ' if lead > 1 else ''}one argument"
+                            f"{' and an optional one' if takes_opt else ''}, got {len(args)}")
+        return args[-1]
+
+    def _what(self, which, n):
+        """how a refused call is named"""
+        return "session " + which
+
+    @staticmethod
+    def _idx_view(idx):
+        """the index buffer as (codebooks, streams, frames) -> the view ``transmit`` hands out, prepared once"""
+        return idx.squeeze(1)
+
+    def _stage_dgram(self, hop, streams, *arrays):
+        """A datagram hop's control words -- budgets and hop numbers, or loss flags --
+        staged as a pool's slot list is, unless the device already holds exactly
+        these (a receiver that loses nothing stages nothing)."""
+        words, = arrays                                  # a session stages one array at a time
+        if hop.staged != words:
+            self._dgram_stager.stage(hop.ctl, words)
+            hop.staged = words
+
+    def _stage_budgets(self, hop, streams, budgets):
+        words = budgets + self._seq
+        if hop.staged != words:
+            self._dgram_stager.stage(hop.ctl, words)
+        hop.staged = None                                # unknown until the hop has run
+
+    def _sent(self, hop, budgets):
+        # the hop's last launch added 1 to every hop number on the device: with the same budgets the
+        # next hop finds its words in place (at the 2^16 wrap they differ, and are staged again)
+        hop.staged = budgets + [q + 1 for q in self._seq]
+        self._seq = [(q + 1) & 0xFFFF for q in self._seq]
+
+    # ---- the per-hop methods, once for sessions and pools ---------------------------------------
+    def _check_input(self, which, slots, x):
+        pl = self.plan
+        L.need_device(x)
+        n = pl.batch if slots is None else len(slots)
+        if tuple(x.shape) != (n, pl.in_channels, pl.chunk):
+            raise L.SelError(f"sel: {self._what(which, n)} takes {(n, pl.in_channels, pl.chunk)}, got "
+                             f"{tuple(x.shape)}")
+
+    def _send(self, which, args):
+        """``transmit`` and ``transmit_packets``: the one replay that writes the index
+        buffer and, with ``wire=True``, the packet buffer -> (its _Hop, n)"""
+        half = self._codes_half(which)
+        slots, x, _ = self._begin(which, args)
+        self._check_input(which, slots, x)
+        if slots is None:
+            n = None
+            half.inp.copy_(x.transpose(1, 2))
+        else:
+            n = self._stage(half, slots)
+            half.inp[:n].copy_(x.transpose(1, 2))
+        half.run("codes")
+        return half.hops["codes"], n
+
+    @torch.no_grad()
+    def transmit(self, *args):
+        """``transmit(x)`` on a session, ``transmit(slots, x)`` on a pool: x (n,
+        in_channels, chunk), for all ``batch`` streams or the n listed slots ->
+        flattened code indices, int64, what ``quantize(encode(x))`` returns (a
+        pool: (codebooks, n, frames)): one replay.  A VIEW of a fixed buffer, valid
+        until the next ``transmit``."""
+        hop, n = self._send("transmit", args)
+        return hop.idx_out if n is None else hop.idx_out[:, :n]
+
+    @torch.no_grad()
+    def receive(self, *args):
+        """``receive(idx)`` on a session, ``receive(slots, idx)`` on a pool: the indices
+        ``transmit`` / ``quantize`` return -> y (n, out_channels, samples), what
+        ``decode(lookup(idx))`` returns (the codes summed in stage order): one replay."""
+        half = self._codes_half("receive")
+        hop = half.hops["codes"]
+        slots, idx, _ = self._begin("receive", args)
+        n = None if slots is None else self._stage(half, slots)
+        _fill_idx(hop.idx if n is None else hop.idx[:, :n * self.plan.frames], idx, self, "receive", n)
+        half.run("codes")
+        return hop.y if n is None else hop.y[:n]
+
+    # ---- the same in the bytes of the wire format (after enable_codes(wire=True)) -----
+    @torch.no_grad()
+    def transmit_packets(self, *args):
+        """``transmit_packets(x)`` / ``transmit_packets(slots, x)`` -> (n, packet_bytes)
+        uint8, ``self.wire``'s packing of what ``transmit`` returns for the same
+        arguments, packet i that of stream i / ``slots[i]``: one replay (the one
+        ``transmit`` runs).  A VIEW of a fixed buffer, valid until the next
+        ``transmit`` / ``transmit_packets``."""
+        hop, n = self._send("transmit_packets", args)
+        return hop.packets if n is None else hop.packets[:n]
+
+    @torch.no_grad()
+    def receive_packets(self, *args):
+        """``receive_packets(p)`` / ``receive_packets(slots, p)``: p (n, packet_bytes)
+        uint8, packet i for stream i / ``slots[i]`` -> y, what ``receive`` returns
+        for the indices in the packets: one replay, with no index tensor in between."""
+        half = self._codes_half("receive_packets")
+        hop = half.hops["wire"]
+        slots, p, _ = self._begin("receive_packets", args)
+        n = None if slots is None else self._stage(half, slots)
+        _fill_packets(hop.packets if n is None else hop.packets[:n], p, self, "receive_packets", n)
+        half.run("wire")
+        return hop.y if n is None else hop.y[:n]
+
+    # ---- the same in datagrams, wire version 2 (after enable_codes(datagrams=True)) -----
+    @torch.no_grad()
+    def transmit_datagrams(self, *args, stages=None):
+        """``transmit_datagrams(x, stages=None)`` on a session, ``transmit_datagrams(slots,
+        x, stages=None)`` on a pool -> (n, stride) uint8, ``stride =
+        self.datagram.stride``: row i starts with the datagram of stream i /
+        ``slots[i]`` for this hop -- the header with the stages carried and the
+        stream's hop number (0 after construction, ``reset()`` and a pool's
+        ``open()``, wrapping at 2^16), then the hop's records of ``stages`` fields
+        -- ``self.datagram.datagram_bytes(stages[i])`` bytes; the bytes of a row
+        beyond that are not written and keep what an earlier hop left there.
+        ``stages``: an int or one int per stream in [1, codebooks], default all; the
+        quantizer's chain stops after that many stages.  One replay, whatever the
+        budgets: they are device words.  A session stages them in front of the
+        replay when they change (its hop numbers advance on the device, behind the
+        quantizer's launch); a pool stages them with its slot list, one control
+        copy per tick.  A VIEW of a fixed buffer: a call invalidates the view the
+        previous ``transmit_datagrams`` returned and, like ``transmit``,
+        ``encode``'s; the views of ``transmit`` / ``transmit_packets`` stay valid."""
+        half = self._codes_half("transmit_datagrams")
+        hop = half.hops["dgram"]
+        slots, x, stages = self._begin("transmit_datagrams", args, stages, True)
+        self._check_input("transmit_datagrams", slots, x)
+        if slots is None:
+            n, streams, inp, out = None, self._all, half.inp, hop.buf
+        else:
+            streams = self.table.check(slots)
+            n = len(streams)
+            inp, out = half.inp[:n], hop.buf[:n]
+        budgets = self._stage_list("transmit_datagrams", stages, len(streams))
+        self._stage_budgets(hop, streams, budgets)
+        inp.copy_(x.transpose(1, 2))
+        half.run("dgram")
+        self._sent(hop, budgets)
+        return out
+
+    @torch.no_grad()
+    def receive_datagrams(self, *args, lost=None):
+        """``receive_datagrams(p, lost=None)`` on a session, ``receive_datagrams(slots, p,
+        lost=None)`` on a pool: the datagrams of one hop -> y, what ``receive``
+        returns for the ids in them (-1 beyond the stages a datagram carries): one
+        replay.  ``p``: a device uint8 (n, stride) tensor as ``transmit_datagrams``
+        returns it, with ``lost``, one flag per stream, marking rows to disregard;
+        or a list of n entries, bytes-like or None for a datagram that did not
+        arrive, which ``self.datagram.assemble`` turns into one host-to-device
+        copy.  A lost stream -- flagged, None, or with a header this receiver
+        refuses -- is concealed: every frame of the hop decodes the last frame's
+        record of the stream's last good datagram (nothing held yet, or the slot
+        opened since: the empty sum), so the decoder's carried state moves on.
+        Nothing is reordered: the caller decides which datagram belongs to which
+        hop.  ``datagram_stats()`` counts."""
+        half = self._codes_half("receive_datagrams")
+        hop = half.hops["dgram"]
+        slots, p, lost = self._begin("receive_datagrams", args, lost, True)
+        if slots is None:
+            streams, dst, y = self._all, hop.buf, hop.y
+        else:
+            streams = self.table.check(slots)
+            dst, y = hop.buf[:len(streams)], hop.y[:len(streams)]
+        self._stage_dgram(hop, streams, self._take_datagrams("receive_datagrams", dst, p, lost, streams))
+        half.run("dgram")
+        return y
+
+    # ---- state: the carries of every half ---------------------------------------------------------
+    def _layers(self):
+        for half in self._halves:
+            for st, c in zip(half.steps, half.carry):
+                if c is not None:
+                    yield st, c, self.generator.get_submodule(st.name)
+
+    def _pad_rows(self, st, m, batches, holds):
+        """a layer's pad_buffer (1 or batch, C, P_ref), checked, channels-last on the carries' device"""
+        pb = m.pad_buffer
+        if pb.shape[0] not in batches or tuple(pb.shape[1:]) != tuple(st.buffer_shape[1:]):
+            raise L.SelError(f"sel: {st.buffer} has shape {tuple(pb.shape)}, {holds.format(st.buffer_shape)}")
+        return pb.to(self._dec.inp.device).transpose(1, 2)
+
+
+def _fill_carry(st, dst, rows):
+    """dst ([batch,] P, C), a carry or one slot row of it <- rows ([batch,] P_ref, C),
+    the reference's pad_buffer channels-last.  The down-sampling conv keeps its
+    2s - 1 samples as 2 phase rows of s samples: 2s rows, the first one zeroed
+    (the extra oldest sample meets a zero weight)."""
+    if st.kind == CO.PACK_FWD_STRIDED:
+        v = dst.view(*dst.shape[:-2], 2 * st.stride, -1)
+        v[..., :1, :].zero_()
+        v[..., 1:, :].copy_(rows)
+    else:
+        dst.copy_(rows)
+
+
+class _SessionBase(_CodesMixin):
+    """Capture, counters and state transfer of StreamSession and VocoderSession."""
+
+    def _capture(self, graph):
+        self.graphed = bool(graph)
+        if graph:
+            for half in self._halves:
+                half.capture()
+            self.reset()   # the warm-up hops ran on zero input; start from zero state
+
+    def datagram_stats(self):
+        """Per stream, since construction / ``reset()``: hops ``received``, ``lost``
+        (``refused``: of those, the malformed ones), ``seq_gaps`` (hop numbers missing
+        between consecutive datagrams seen), ``concealed_run`` (the current run of
+        concealed hops) and the last datagram's ``stages`` and ``seq``.  Headers are
+        read on the host only: for datagrams given as a device tensor ``refused``,
+        ``seq_gaps``, ``stages`` and ``seq`` do not move."""
+        if not self._dgram_enabled:
+            raise L.SelError("sel: datagram_stats needs enable_codes(datagrams=True) first")
+        return [dict(s) for s in self._dstats]
+
+    def carries(self):
+        """{pad_buffer key: carry tensor (batch, P, C), channels-last} -- the live state."""
+        return {st.buffer: c for st, c, _ in self._layers()}
+
+    @torch.no_grad()
+    def reset(self):
+        for half in self._halves:
+            half.zero()
+        for i in range(len(self._seq or ())):
+            self._clear_stream(i)
+
+    @torch.no_grad()
+    def load_state(self):
+        """carries <- the generator's pad_buffers ((1 or batch, C, P), broadcast to batch)."""
+        for st, c, m in self._layers():
+            rows = self._pad_rows(st, m, (1, c.shape[0]), "the session holds {} per stream")
+            _fill_carry(st, c, rows.expand(c.shape[0], -1, -1))
+
+    @torch.no_grad()
+    def store_state(self):
+        """The generator's pad_buffers <- carries, in the reference's shapes (fp32)."""
+        for st, c, m in self._layers():
+            v = c.view(c.shape[0], -1, st.buffer_shape[1])
+            if st.kind == CO.PACK_FWD_STRIDED:
+                v = v[:, 1:]
+            m.pad_buffer = v.transpose(1, 2).float().contiguous()
+
+
+class StreamSession(_SessionBase):
     """One streaming endpoint state: ``batch`` parallel streams, ``chunk`` samples per hop.
 
     ``encode(x) -> z``, ``quantize(z) -> idx``, ``lookup(idx) -> zq`` and
@@ -519,13 +793,10 @@ class StreamSession(_CodesMixin):
         with torch.no_grad():
             self._enc = _Half(pl.encode, generator, batch, pl.in_channels, self.dtype, dev)
             self._dec = _Half(pl.decode, generator, batch, pl.dec_in_channels, self.dtype, dev)
+            self._halves = (self._enc, self._dec)
             if hasattr(generator, "quantizer") and not hasattr(generator.quantizer.codebook, "codebook_size"):
                 generator.quantizer.initial()
-            self.graphed = bool(graph)
-            if graph:
-                self._enc.capture()
-                self._dec.capture()
-                self.reset()   # the warm-up hops ran on zero input; start from zero state
+            self._capture(graph)
 
     # ---- the four methods of the reference's streamer -------------------------
     @torch.no_grad()
@@ -562,212 +833,19 @@ class StreamSession(_CodesMixin):
         self._dec.inp.copy_(src)
         return self._dec.run().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
 
-    # ---- the same with the code indices inside the hop (after enable_codes) -----
-    @torch.no_grad()
-    def transmit(self, x):
-        """x (batch, in_channels, chunk) -> flattened code indices, int64, what
-        ``quantize(encode(x))`` returns: one replay.  A VIEW of a fixed buffer,
-        valid until the next ``transmit``."""
-        half = self._codes_half("transmit")
-        pl = self.plan
-        L.need_device(x)
-        if tuple(x.shape) != (pl.batch, pl.in_channels, pl.chunk):
-            raise L.SelError(f"sel: session transmit takes {(pl.batch, pl.in_channels, pl.chunk)}, got {tuple(x.shape)}")
-        half.inp.copy_(x.transpose(1, 2))
-        half.run_codes()
-        return half.idx.view(-1, pl.batch, pl.frames).squeeze(1)
-
-    @torch.no_grad()
-    def receive(self, idx):
-        """The indices ``transmit`` / ``quantize`` return -> y, what
-        ``decode(lookup(idx))`` returns (the codes summed in stage order): one replay."""
-        half = self._codes_half("receive")
-        pl = self.plan
-        _fill_idx(half.idx, idx, "session receive")
-        return half.run_codes().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
-
-    # ---- the same in the bytes of the wire format (after enable_codes(wire=True)) -----
-    @torch.no_grad()
-    def transmit_packets(self, x):
-        """x (batch, in_channels, chunk) -> (batch, packet_bytes) uint8, ``self.wire``'s
-        packing of what ``transmit(x)`` returns: one replay (the one ``transmit``
-        runs).  A VIEW of a fixed buffer, valid until the next ``transmit`` /
-        ``transmit_packets``."""
-        half = self._codes_half("transmit_packets")
-        pl = self.plan
-        L.need_device(x)
-        if tuple(x.shape) != (pl.batch, pl.in_channels, pl.chunk):
-            raise L.SelError(f"sel: session transmit_packets takes {(pl.batch, pl.in_channels, pl.chunk)}, got "
-                             f"{tuple(x.shape)}")
-        half.inp.copy_(x.transpose(1, 2))
-        half.run_codes()
-        return half.wire_buf.view(pl.batch, self.wire.packet_bytes)
-
-    @torch.no_grad()
-    def receive_packets(self, p):
-        """p (batch, packet_bytes) uint8 -> y, what ``receive`` returns for the
-        indices in the packets: one replay, with no index tensor in between."""
-        half = self._codes_half("receive_packets")
-        pl = self.plan
-        _fill_packets(half.wire_buf.view(pl.batch, self.wire.packet_bytes), p, "session receive_packets")
-        return half.run_wire().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
-
-    # ---- the same in datagrams, wire version 2 (after enable_codes(datagrams=True)) -----
-    @torch.no_grad()
-    def transmit_datagrams(self, x, stages=None):
-        """x (batch, in_channels, chunk) -> (batch, stride) uint8, ``stride =
-        self.datagram.stride``: row i starts with stream i's datagram for this hop
-        -- the header with the stages carried and the stream's hop number (0 after
-        construction and ``reset()``, wrapping at 2^16), then the hop's records of
-        ``stages`` fields -- ``self.datagram.datagram_bytes(stages[i])`` bytes; the
-        bytes of a row beyond that are not written and keep what an earlier hop
-        left there.  ``stages``: an int or one int per stream in [1, codebooks],
-        default all; the quantizer's chain stops after that many stages.  One
-        replay, whatever the budgets: they are device words, staged in front of it
-        when they change (the hop numbers advance on the device, behind the
-        quantizer's launch).  A VIEW of a fixed buffer: a call invalidates the view the previous
-        ``transmit_datagrams`` returned and, like ``transmit``, ``encode``'s; the
-        views of ``transmit`` / ``transmit_packets`` stay valid."""
-        half = self._codes_half("transmit_datagrams")
-        pl = self.plan
-        L.need_device(x)
-        if tuple(x.shape) != (pl.batch, pl.in_channels, pl.chunk):
-            raise L.SelError(f"sel: session transmit_datagrams takes {(pl.batch, pl.in_channels, pl.chunk)}, got "
-                             f"{tuple(x.shape)}")
-        budgets = self._stage_list("session transmit_datagrams", stages, pl.batch)
-        self._stage_words(half, budgets + self._seq)
-        half.dgram_staged = None                         # unknown until the hop has run
-        half.inp.copy_(x.transpose(1, 2))
-        half.run_dgram()
-        # the hop's last launch added 1 to every hop number on the device: with the same budgets the
-        # next hop finds its words in place (at the 2^16 wrap they differ, and are staged again)
-        half.dgram_staged = budgets + [q + 1 for q in self._seq]
-        self._seq = [(q + 1) & 0xFFFF for q in self._seq]
-        return half.dgram_buf
-
-    @torch.no_grad()
-    def receive_datagrams(self, p, lost=None):
-        """The datagrams of one hop -> y, what ``receive`` returns for the ids in
-        them (-1 beyond the stages a datagram carries): one replay.  ``p``: a
-        device uint8 (batch, stride) tensor as ``transmit_datagrams`` returns it,
-        with ``lost``, one flag per stream, marking rows to disregard; or a list
-        of ``batch`` entries, bytes-like or None for a datagram that did not
-        arrive, which ``self.datagram.assemble`` turns into one host-to-device
-        copy.  A lost stream -- flagged, None, or with a header this receiver
-        refuses -- is concealed: every frame of the hop decodes the last frame's
-        record of the stream's last good datagram (nothing held yet: the empty
-        sum), so the decoder's carried state moves on.  Nothing is reordered: the
-        caller decides which datagram belongs to which hop.  ``datagram_stats()``
-        counts."""
-        half = self._codes_half("receive_datagrams")
-        pl = self.plan
-        flags = self._take_datagrams("session receive_datagrams", half.dgram_buf, p, lost, range(pl.batch))
-        self._stage_words(half, flags)
-        return half.run_dgram().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
-
-    def _stage_words(self, half, words):
-        """A session half's control words, staged as a pool's slot list is -- unless the
-        device already holds exactly these (a receiver that loses nothing stages nothing)."""
-        if half.dgram_staged != words:
-            self._dgram_stager.stage(half.dgram_ctl, words)
-            half.dgram_staged = words
-
-    def datagram_stats(self):
-        """Per stream, since construction / ``reset()``: hops ``received``, ``lost``
-        (``refused``: of those, the malformed ones), ``seq_gaps`` (hop numbers missing
-        between consecutive datagrams seen), ``concealed_run`` (the current run of
-        concealed hops) and the last datagram's ``stages`` and ``seq``.  Headers are
-        read on the host only: for datagrams given as a device tensor ``refused``,
-        ``seq_gaps``, ``stages`` and ``seq`` do not move."""
-        if not self._dgram_enabled:
-            raise L.SelError("sel: datagram_stats needs enable_codes(datagrams=True) first")
-        return [dict(s) for s in self._dstats]
-
-    def _reset_datagrams(self):
-        for i in range(len(self._seq or ())):
-            self._clear_stream(i)
-
-    # ---- state ------------------------------------------------------------------
-    def _layers(self):
-        for half in (self._enc, self._dec):
-            for st, c in zip(half.steps, half.carry):
-                if c is not None:
-                    yield st, c, self.generator.get_submodule(st.name)
-
-    def carries(self):
-        """{pad_buffer key: carry tensor (batch, P, C), channels-last} -- the live state."""
-        return {st.buffer: c for st, c, _ in self._layers()}
-
-    @torch.no_grad()
-    def reset(self):
-        self._enc.zero()
-        self._dec.zero()
-        self._reset_datagrams()
-
-    @torch.no_grad()
-    def load_state(self):
-        """carries <- the generator's pad_buffers ((1 or batch, C, P), broadcast to batch)."""
-        for st, c, m in self._layers():
-            pb = m.pad_buffer
-            if pb.shape[0] not in (1, c.shape[0]) or tuple(pb.shape[1:]) != tuple(st.buffer_shape[1:]):
-                raise L.SelError(f"sel: {st.buffer} has shape {tuple(pb.shape)}, the session holds "
-                                 f"{st.buffer_shape} per stream")
-            rows = pb.to(c.device).transpose(1, 2).expand(c.shape[0], -1, -1)      # (batch, P_ref, Cin)
-            if st.kind == CO.PACK_FWD_STRIDED:
-                # 2s samples as 2 phase rows; the extra oldest sample meets a zero weight
-                v = c.view(c.shape[0], 2 * st.stride, -1)
-                v[:, :1].zero_()
-                v[:, 1:].copy_(rows)
-            else:
-                c.copy_(rows)
-
-    @torch.no_grad()
-    def store_state(self):
-        """The generator's pad_buffers <- carries, in the reference's shapes (fp32)."""
-        for st, c, m in self._layers():
-            v = c.view(c.shape[0], -1, st.buffer_shape[1])
-            if st.kind == CO.PACK_FWD_STRIDED:
-                v = v[:, 1:]
-            m.pad_buffer = v.transpose(1, 2).float().contiguous()
-
 
 class _VocoderHalf(_Half):
-    """The launches of a vocoder ``decode`` on fixed buffers (capture / run / zero as _Half)."""
+    """The launches of a vocoder ``decode`` on fixed buffers: _Half on the grouped step kernel."""
+    _step = staticmethod(SO.hfg_conv_step)
 
-    def __init__(self, steps, generator, batch, in_channels, dtype, device):
+    @staticmethod
+    def _weights(generator, st, dtype):
         from . import hfgops as HF
-        self.steps = steps
-        self.batch = batch
-        self.inp = torch.zeros((batch, steps[0].T, in_channels), dtype=dtype, device=device)
-        self.descs, self.wps, self.biases, self.outs = [], [], [], []
-        self.carry, self.carry_out = [], []
-        for i, st in enumerate(steps):
-            m = generator.get_submodule(st.conv)
-            self.descs.append(st.desc(batch))
-            self.wps.append(HF.packed(m, st.kind, st.stride, dtype))
-            self.biases.append(m.bias.detach().float().contiguous() if st.bias_period else None)
-            if st.out != i:
-                self.outs.append(self.outs[st.out])    # accumulates into an earlier step's buffer
-            else:
-                self.outs.append(torch.zeros((batch * st.T, st.N), dtype=torch.float32 if st.out_float else dtype,
-                                             device=device))
-            if st.carry_shape is None:
-                self.carry.append(None)
-                self.carry_out.append(None)
-            else:
-                self.carry.append(torch.zeros(st.carry_shape, dtype=dtype, device=device))
-                self.carry_out.append(torch.zeros(st.carry_shape, dtype=dtype, device=device))
-        self.pairs = [(o, c) for o, c in zip(self.carry_out, self.carry) if c is not None]
-        self.graph = None
-
-    def launch(self):
-        for i, st in enumerate(self.steps):
-            SO.hfg_conv_step(self.descs[i], self.carry[i], self._buf(st.src), self.wps[i], self.biases[i],
-                             None if st.res is None else self._buf(st.res), self.outs[i], self.carry_out[i])
-        SO.commit(self.pairs)
+        m = generator.get_submodule(st.conv)
+        return HF.packed(m, st.kind, st.stride, dtype), m.bias.detach().float().contiguous() if st.bias_period else None
 
 
-class VocoderSession(_CodesMixin):
+class VocoderSession(_SessionBase):
     """The receiver's streaming state for a HiFi-GAN vocoder ``StreamGenerator``:
     ``batch`` parallel streams, ``frames`` code frames per hop.
 
@@ -805,10 +883,8 @@ class VocoderSession(_CodesMixin):
         pl = self.plan
         with torch.no_grad():
             self._dec = _VocoderHalf(pl.steps, generator, batch, pl.in_channels, self.dtype, p.device)
-            self.graphed = bool(graph)
-            if graph:
-                self._dec.capture()
-                self.reset()   # the warm-up hops ran on zero input; start from zero state
+            self._halves = (self._dec,)
+            self._capture(graph)
 
     @torch.no_grad()
     def lookup(self, idx):
@@ -827,49 +903,6 @@ class VocoderSession(_CodesMixin):
             raise L.SelError(f"sel: session decode takes {(pl.batch, pl.frames, pl.in_channels)}, got {tuple(c.shape)}")
         self._dec.inp.copy_(self.generator.decode_norm(c))
         return self._dec.run().view(pl.batch, pl.out_samples, pl.out_channels).transpose(1, 2)
-
-    # after enable_codes(): lookup, decode_norm and decode as one replay (transmit: always a SelError)
-    transmit = StreamSession.transmit
-    receive = StreamSession.receive
-    transmit_packets = StreamSession.transmit_packets
-    receive_packets = StreamSession.receive_packets
-    transmit_datagrams = StreamSession.transmit_datagrams
-    receive_datagrams = StreamSession.receive_datagrams
-    datagram_stats = StreamSession.datagram_stats
-    _reset_datagrams = StreamSession._reset_datagrams
-    _stage_words = StreamSession._stage_words
-
-    # ---- state ------------------------------------------------------------------
-    def _layers(self):
-        for st, c in zip(self._dec.steps, self._dec.carry):
-            if c is not None:
-                yield st, c, self.generator.get_submodule(st.name)
-
-    def carries(self):
-        """{pad_buffer key: carry tensor (batch, P, C), channels-last} -- the live state."""
-        return {st.buffer: c for st, c, _ in self._layers()}
-
-    @torch.no_grad()
-    def reset(self):
-        self._dec.zero()
-        self._reset_datagrams()
-
-    @torch.no_grad()
-    def load_state(self):
-        """carries <- the generator's pad_buffers ((1 or batch, C, P), broadcast to batch)."""
-        for st, c, m in self._layers():
-            pb = m.pad_buffer
-            if pb.shape[0] not in (1, c.shape[0]) or tuple(pb.shape[1:]) != tuple(st.buffer_shape[1:]):
-                raise L.SelError(f"sel: {st.buffer} has shape {tuple(pb.shape)}, the session holds "
-                                 f"{st.buffer_shape} per stream")
-            c.copy_(pb.to(c.device).transpose(1, 2).expand(c.shape[0], -1, -1))
-
-    @torch.no_grad()
-    def store_state(self):
-        """The generator's pad_buffers <- carries, in the reference's shapes (fp32)."""
-        for _, c, m in self._layers():
-            m.pad_buffer = c.transpose(1, 2).float().contiguous()
-
 
 # ---- stream pools: independent streams on the slot-indexed step kernels -------------------------
 class _Stager:
@@ -922,13 +955,14 @@ class _PoolMixin:
                     lst[i] = torch.zeros((self.nslots,) + tuple(c.shape[1:]), dtype=c.dtype, device=device)
         self.pairs = [(o, c) for o, c in zip(self.carry_out, self.carry) if c is not None]
 
-    def launch(self):
+    def _launch_steps(self):
         step = self._step
         for i, st in enumerate(self.steps):
             step(self.descs[i], self.carry[i], self.carry_out[i], self.slots, self.n_active, self._buf(st.src),
                  self.wps[i], self.biases[i], None if st.res is None else self._buf(st.res), self.outs[i],
                  nslots=self.nslots)
         SO.copy_slots(self.pairs, self.slots, self.slots, self.n_active)
+
 
 class _PoolHalf(_PoolMixin, _Half):
     _step = staticmethod(SO.conv_step_pool)
@@ -980,118 +1014,40 @@ class _PoolBase(_CodesMixin):
         if half.graph is not None:
             half.ctl.zero_()
 
-    @torch.no_grad()
-    def transmit(self, slots, x):
-        """x (n, in_channels, chunk) for the n listed slots -> flattened code indices
-        (codebooks, n, frames), what ``quantize(encode(slots, x))`` returns: one
-        replay.  A VIEW of a fixed buffer, valid until the next ``transmit``."""
-        half = self._codes_half("transmit")
-        pl = self.plan
-        L.need_device(x)
-        if tuple(x.shape) != (len(slots), pl.in_channels, pl.chunk):
-            raise L.SelError(f"sel: pool transmit takes {(len(slots), pl.in_channels, pl.chunk)} for {len(slots)} "
-                             f"slots, got {tuple(x.shape)}")
-        n = self._stage(half, slots)
-        half.inp[:n].copy_(x.transpose(1, 2))
-        half.run_codes()
-        return half.idx.view(-1, self.capacity, pl.frames)[:, :n]
+    # ---- the hooks of the per-hop methods (_CodesMixin): a slot list in front, n of capacity rows ----
+    def _begin(self, which, args, opt=None, takes_opt=False):
+        if len(args) != 2:
+            opt = self._optional(which, args, 2, opt, takes_opt)
+        return args[0], args[1], opt
 
-    @torch.no_grad()
-    def receive(self, slots, idx):
-        """idx (codebooks, n, frames), what ``transmit`` / ``quantize`` return, for the
-        n listed slots -> y (n, out_channels, samples), what ``decode(slots,
-        lookup(idx))`` returns (the codes summed in stage order): one replay."""
-        half = self._codes_half("receive")
-        pl = self.plan
-        n = self._stage(half, slots)
-        _fill_idx(half.idx[:, :n * pl.frames], idx, f"pool receive for {n} slots")
-        out = half.run_codes()
-        return out.view(self.capacity, pl.out_samples, pl.out_channels)[:n].transpose(1, 2)
+    def _what(self, which, n):
+        return f"pool {which} for {n} slots"
 
-    @torch.no_grad()
-    def transmit_packets(self, slots, x):
-        """x (n, in_channels, chunk) for the n listed slots -> (n, packet_bytes) uint8,
-        ``self.wire``'s packing of what ``transmit(slots, x)`` returns, packet i that
-        of ``slots[i]``: one replay.  A VIEW of a fixed buffer, valid until the next
-        ``transmit`` / ``transmit_packets``."""
-        half = self._codes_half("transmit_packets")
-        pl = self.plan
-        L.need_device(x)
-        if tuple(x.shape) != (len(slots), pl.in_channels, pl.chunk):
-            raise L.SelError(f"sel: pool transmit_packets takes {(len(slots), pl.in_channels, pl.chunk)} for "
-                             f"{len(slots)} slots, got {tuple(x.shape)}")
-        n = self._stage(half, slots)
-        half.inp[:n].copy_(x.transpose(1, 2))
-        half.run_codes()
-        return half.wire_buf.view(self.capacity, self.wire.packet_bytes)[:n]
+    @staticmethod
+    def _idx_view(idx):
+        return idx
 
-    @torch.no_grad()
-    def receive_packets(self, slots, p):
-        """p (n, packet_bytes) uint8, packet i for ``slots[i]`` -> y (n, out_channels,
-        samples), what ``receive`` returns for the indices in the packets: one replay."""
-        half = self._codes_half("receive_packets")
-        pl = self.plan
-        n = self._stage(half, slots)
-        _fill_packets(half.wire_buf.view(self.capacity, self.wire.packet_bytes)[:n], p,
-                      f"pool receive_packets for {n} slots")
-        out = half.run_wire()
-        return out.view(self.capacity, pl.out_samples, pl.out_channels)[:n].transpose(1, 2)
-
-    # ---- the same in datagrams (after enable_codes(datagrams=True)) ------------------------------
     def _dgram_words(self, half, B, arrays, device):
         # behind the slot list, in the tensor the half's graphs already read: a tick is one copy
         cap = self.capacity
         views = [half.ctl_all[1 + (1 + i) * cap:1 + (2 + i) * cap] for i in range(arrays)]
         return half.ctl_all[:1 + (1 + arrays) * cap], views
 
-    def _stage_dgram(self, half, slots, *arrays):
+    def _stage_dgram(self, hop, slots, *arrays):
         """[n, slots..., array 0..., array 1...], each padded to capacity, in one copy."""
         pad = [0] * (self.capacity - len(slots))
         words = [len(slots)] + slots + pad
         for a in arrays:
             words += a + pad
-        self._stager.stage(half.dgram_ctl, words)
-        return len(slots)
+        self._stager.stage(hop.ctl, words)
 
-    @torch.no_grad()
-    def transmit_datagrams(self, slots, x, stages=None):
-        """x (n, in_channels, chunk) for the n listed slots -> (n, stride) uint8, row i
-        starting with the datagram of ``slots[i]`` for this hop, as a session's
-        ``transmit_datagrams`` writes it; ``stages``: an int or one int per listed
-        slot.  A slot's hop number starts at 0 at ``open()``.  One replay and one
-        control copy, whatever the slots and budgets.  A VIEW of a fixed buffer: a
-        call invalidates the view of the previous ``transmit_datagrams`` (and
-        ``encode``'s); those of ``transmit`` / ``transmit_packets`` stay valid."""
-        half = self._codes_half("transmit_datagrams")
-        pl = self.plan
-        L.need_device(x)
-        if tuple(x.shape) != (len(slots), pl.in_channels, pl.chunk):
-            raise L.SelError(f"sel: pool transmit_datagrams takes {(len(slots), pl.in_channels, pl.chunk)} for "
-                             f"{len(slots)} slots, got {tuple(x.shape)}")
-        slots = self.table.check(slots)
-        budgets = self._stage_list("pool transmit_datagrams", stages, len(slots))
-        n = self._stage_dgram(half, slots, budgets, [self._seq[s] & 0xFFFF for s in slots])
+    def _stage_budgets(self, hop, slots, budgets):
+        self._stage_dgram(hop, slots, budgets, [self._seq[s] & 0xFFFF for s in slots])
         for s in slots:
             self._seq[s] += 1
-        half.inp[:n].copy_(x.transpose(1, 2))
-        half.run_dgram()
-        return half.dgram_buf[:n]
 
-    @torch.no_grad()
-    def receive_datagrams(self, slots, p, lost=None):
-        """The datagrams of one tick, entry i for ``slots[i]`` -> y (n, out_channels,
-        samples): a session's ``receive_datagrams`` per listed slot, each slot
-        concealing its own lost hops from its own held record (cleared at
-        ``open()``).  ``p``: a device uint8 (n, stride) tensor with optional
-        ``lost`` flags, or a list of n bytes-like / None entries.  One replay."""
-        half = self._codes_half("receive_datagrams")
-        pl = self.plan
-        slots = self.table.check(slots)
-        n = len(slots)
-        flags = self._take_datagrams(f"pool receive_datagrams for {n} slots", half.dgram_buf[:n], p, lost, slots)
-        self._stage_dgram(half, slots, flags)
-        out = half.run_dgram()
-        return out.view(self.capacity, pl.out_samples, pl.out_channels)[:n].transpose(1, 2)
+    def _sent(self, hop, budgets):
+        """the hop numbers are host words, staged with every tick"""
 
     def datagram_stats(self, slot):
         """The counters of a session's ``datagram_stats()`` for one open slot, since its ``open()``."""
@@ -1099,12 +1055,6 @@ class _PoolBase(_CodesMixin):
             raise L.SelError("sel: datagram_stats needs enable_codes(datagrams=True) first")
         slot, = self.table.check([slot])
         return dict(self._dstats[slot])
-
-    def _layers(self):
-        for half in self._halves:
-            for st, c in zip(half.steps, half.carry):
-                if c is not None:
-                    yield st, c, self.generator.get_submodule(st.name)
 
     @torch.no_grad()
     def open(self):
@@ -1134,12 +1084,11 @@ class _PoolBase(_CodesMixin):
         for c in self._carries:
             c[self.capacity].zero_()
 
-    def _template_rows(self, st, c, m):
-        pb = m.pad_buffer
-        if pb.shape[0] != 1 or tuple(pb.shape[1:]) != tuple(st.buffer_shape[1:]):
-            raise L.SelError(f"sel: {st.buffer} has shape {tuple(pb.shape)}, the pool's template holds "
-                             f"{st.buffer_shape}")
-        return pb.to(c.device).transpose(1, 2)[0]      # (P_ref, Cin)
+    @torch.no_grad()
+    def load_state(self):
+        """template <- the generator's pad_buffers ((1, C, P)), as a session's load_state fills a carry."""
+        for st, c, m in self._layers():
+            _fill_carry(st, c[self.capacity], self._pad_rows(st, m, (1,), "the pool's template holds {}")[0])
 
 
 class StreamPool(_PoolBase):
@@ -1224,20 +1173,6 @@ class StreamPool(_PoolBase):
         out = self._dec.run()
         return out.view(self.capacity, pl.out_samples, pl.out_channels)[:n].transpose(1, 2)
 
-    @torch.no_grad()
-    def load_state(self):
-        """template <- the generator's pad_buffers ((1, C, P)), as StreamSession.load_state fills a carry."""
-        for st, c, m in self._layers():
-            rows = self._template_rows(st, c, m)
-            t = c[self.capacity]
-            if st.kind == CO.PACK_FWD_STRIDED:
-                # 2s samples as 2 phase rows; the extra oldest sample meets a zero weight
-                v = t.view(2 * st.stride, -1)
-                v[:1].zero_()
-                v[1:].copy_(rows)
-            else:
-                t.copy_(rows)
-
 
 class VocoderPool(_PoolBase):
     """``capacity`` independent streams of one HiFi-GAN vocoder ``StreamGenerator``,
@@ -1281,9 +1216,3 @@ class VocoderPool(_PoolBase):
         self._dec.inp[:n].copy_(self.generator.decode_norm(c))
         out = self._dec.run()
         return out.view(self.capacity, pl.out_samples, pl.out_channels)[:n].transpose(1, 2)
-
-    @torch.no_grad()
-    def load_state(self):
-        """template <- the generator's pad_buffers ((1, C, P))."""
-        for st, c, m in self._layers():
-            c[self.capacity].copy_(self._template_rows(st, c, m))

@@ -234,6 +234,60 @@ def _count_operand(what, n_active):
         raise L.SelError(f"sel: {what} takes a contiguous int32 device tensor for n_active")
 
 
+def _rows_per_sample(what, rows, rows_per_sample):
+    if rows_per_sample < 1 or rows % rows_per_sample:
+        raise L.SelError(f"sel: {what} rows ({rows}) is not a multiple of rows_per_sample ({rows_per_sample})")
+
+
+def _quantizer_operands(what, z, embeds, idx, zq, rows_per_sample, need_idx=False):
+    """The operands the three quantizer launches share -> (S, D, K, rows)."""
+    if embeds.dim() != 3 or embeds.dtype != torch.float32 or not embeds.is_contiguous():
+        raise L.SelError(f"sel: {what} takes a contiguous fp32 (S, D, K) stack, got {embeds.dtype} "
+                         f"{tuple(embeds.shape)}")
+    S, D, K = embeds.shape
+    if z.dim() != 2 or z.shape[1] != D or z.dtype != torch.float32 or not z.is_contiguous():
+        raise L.SelError(f"sel: {what} takes contiguous fp32 rows (rows, {D}), got {z.dtype} {tuple(z.shape)}")
+    rows = z.shape[0]
+    if (need_idx or idx is not None) and (idx.dtype != torch.int64 or not idx.is_contiguous()
+                                          or tuple(idx.shape) != (S, rows)):
+        raise L.SelError(f"sel: {what} writes a contiguous int64 idx of shape {(S, rows)}, got {idx.dtype} "
+                         f"{tuple(idx.shape)}")
+    if zq is not None and (zq.dtype != torch.float32 or not zq.is_contiguous() or zq.shape != z.shape):
+        raise L.SelError(f"sel: {what} writes a contiguous fp32 zq of shape {tuple(z.shape)}")
+    _rows_per_sample(what, rows, rows_per_sample)
+    return S, D, K, rows
+
+
+def _lookup_codebook(what, codebook, codebooks=None):
+    """The flat codebook of the three lookup launches -> (ncodes, D), and with the
+    stage count ``codebooks`` of the packed forms -> (S, K, D)."""
+    if codebook.dim() != 2 or codebook.dtype != torch.float32 or not codebook.is_contiguous():
+        raise L.SelError(f"sel: {what} takes a contiguous fp32 (ncodes, D) codebook, got {codebook.dtype} "
+                         f"{tuple(codebook.shape)}")
+    ncodes, D = codebook.shape
+    if codebooks is None:
+        return ncodes, D
+    S = int(codebooks)
+    if S < 1 or ncodes % S or ncodes < S:
+        raise L.SelError(f"sel: {what}: a codebook of {ncodes} rows is not {S} stages of one size")
+    return S, ncodes // S, D
+
+
+def _lookup_outputs(what, out, rows, D, mean, scale, idx_out=None, S=None):
+    """out, the optional idx_out and mean / scale of the three lookup launches."""
+    if out.dtype not in (torch.float32, torch.bfloat16) or not out.is_contiguous() or out.numel() != rows * D:
+        raise L.SelError(f"sel: {what} writes {rows} contiguous fp32 / bf16 rows of {D}, got {out.dtype} "
+                         f"{tuple(out.shape)}")
+    if idx_out is not None and (idx_out.dtype != torch.int64 or not idx_out.is_contiguous()
+                                or tuple(idx_out.shape) != (S, rows)):
+        raise L.SelError(f"sel: {what} writes a contiguous int64 idx_out of shape {(S, rows)}")
+    if (mean is None) != (scale is None):
+        raise L.SelError(f"sel: {what} takes mean and scale together or not at all")
+    for t in (mean, scale):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != D):
+            raise L.SelError(f"sel: {what} takes contiguous fp32 mean / scale of {D} elements")
+
+
 def rvq_step(z, embeds, idx, rows_per_sample=1, n_active=None, flatten=True, zq=None):
     """One sel_rvq_step launch on the current stream: z (rows, D) fp32 rows ->
     idx (S, rows) int64 picks (flatten: + s*K, ids into the flat codebook) and,
@@ -241,20 +295,7 @@ def rvq_step(z, embeds, idx, rows_per_sample=1, n_active=None, flatten=True, zq=
     n_active (1 int32, DEVICE) makes the first n_active * rows_per_sample rows
     the only ones read and written.  Nothing is allocated.  Returns idx."""
     L.need_device(z, embeds, idx, n_active, zq)
-    if embeds.dim() != 3 or embeds.dtype != torch.float32 or not embeds.is_contiguous():
-        raise L.SelError(f"sel: rvq_step takes a contiguous fp32 (S, D, K) stack, got {embeds.dtype} "
-                         f"{tuple(embeds.shape)}")
-    S, D, K = embeds.shape
-    if z.dim() != 2 or z.shape[1] != D or z.dtype != torch.float32 or not z.is_contiguous():
-        raise L.SelError(f"sel: rvq_step takes contiguous fp32 rows (rows, {D}), got {z.dtype} {tuple(z.shape)}")
-    rows = z.shape[0]
-    if idx.dtype != torch.int64 or not idx.is_contiguous() or tuple(idx.shape) != (S, rows):
-        raise L.SelError(f"sel: rvq_step writes a contiguous int64 idx of shape {(S, rows)}, got {idx.dtype} "
-                         f"{tuple(idx.shape)}")
-    if zq is not None and (zq.dtype != torch.float32 or not zq.is_contiguous() or zq.shape != z.shape):
-        raise L.SelError(f"sel: rvq_step writes a contiguous fp32 zq of shape {tuple(z.shape)}")
-    if rows_per_sample < 1 or rows % rows_per_sample:
-        raise L.SelError(f"sel: rvq_step rows ({rows}) is not a multiple of rows_per_sample ({rows_per_sample})")
+    S, D, K, rows = _quantizer_operands("rvq_step", z, embeds, idx, zq, rows_per_sample, need_idx=True)
     _count_operand("rvq_step", n_active)
     L.call("sel_rvq_step", L.ptr(z), rows, rows_per_sample, D, L.ptr(embeds), S, K, L.ptr(n_active),
            int(bool(flatten)), L.ptr(idx), L.ptr(zq), L.stream())
@@ -268,25 +309,13 @@ def rvq_lookup_step(idx, codebook, out, rows_per_sample=1, mean=None, scale=None
     then (acc - mean) / scale when both are given (D fp32 each), then rounded to
     out's dtype.  n_active as in rvq_step.  Nothing is allocated.  Returns out."""
     L.need_device(idx, codebook, out, mean, scale, n_active)
-    if codebook.dim() != 2 or codebook.dtype != torch.float32 or not codebook.is_contiguous():
-        raise L.SelError(f"sel: rvq_lookup_step takes a contiguous fp32 (ncodes, D) codebook, got {codebook.dtype} "
-                         f"{tuple(codebook.shape)}")
-    ncodes, D = codebook.shape
+    ncodes, D = _lookup_codebook("rvq_lookup_step", codebook)
     if idx.dim() != 2 or idx.dtype != torch.int64 or not idx.is_contiguous():
         raise L.SelError(f"sel: rvq_lookup_step takes a contiguous int64 idx (S, rows), got {idx.dtype} "
                          f"{tuple(idx.shape)}")
     S, rows = idx.shape
-    if out.dtype not in (torch.float32, torch.bfloat16) or not out.is_contiguous() or out.numel() != rows * D:
-        raise L.SelError(f"sel: rvq_lookup_step writes {rows} contiguous fp32 / bf16 rows of {D}, got {out.dtype} "
-                         f"{tuple(out.shape)}")
-    if (mean is None) != (scale is None):
-        raise L.SelError("sel: rvq_lookup_step takes mean and scale together or not at all")
-    for t in (mean, scale):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != D):
-            raise L.SelError(f"sel: rvq_lookup_step takes contiguous fp32 mean / scale of {D} elements")
-    if rows_per_sample < 1 or rows % rows_per_sample:
-        raise L.SelError(f"sel: rvq_lookup_step rows ({rows}) is not a multiple of rows_per_sample "
-                         f"({rows_per_sample})")
+    _lookup_outputs("rvq_lookup_step", out, rows, D, mean, scale)
+    _rows_per_sample("rvq_lookup_step", rows, rows_per_sample)
     _count_operand("rvq_lookup_step", n_active)
     L.call("sel_rvq_lookup_step", L.ptr(idx), rows, rows_per_sample, S, ncodes, D, L.ptr(codebook), L.ptr(mean),
            L.ptr(scale), L.ptr(n_active), CO._code(out.dtype), L.ptr(out), L.stream())
@@ -309,20 +338,7 @@ def rvq_step_wire(z, embeds, wire, rows_per_sample=1, n_active=None, flatten=Tru
     record into wire (rows, frame_bytes) uint8 -- dense rows, any byte alignment.
     Nothing is allocated.  Returns wire."""
     L.need_device(z, embeds, wire, idx, n_active, zq)
-    if embeds.dim() != 3 or embeds.dtype != torch.float32 or not embeds.is_contiguous():
-        raise L.SelError(f"sel: rvq_step_wire takes a contiguous fp32 (S, D, K) stack, got {embeds.dtype} "
-                         f"{tuple(embeds.shape)}")
-    S, D, K = embeds.shape
-    if z.dim() != 2 or z.shape[1] != D or z.dtype != torch.float32 or not z.is_contiguous():
-        raise L.SelError(f"sel: rvq_step_wire takes contiguous fp32 rows (rows, {D}), got {z.dtype} {tuple(z.shape)}")
-    rows = z.shape[0]
-    if idx is not None and (idx.dtype != torch.int64 or not idx.is_contiguous() or tuple(idx.shape) != (S, rows)):
-        raise L.SelError(f"sel: rvq_step_wire writes a contiguous int64 idx of shape {(S, rows)}, got {idx.dtype} "
-                         f"{tuple(idx.shape)}")
-    if zq is not None and (zq.dtype != torch.float32 or not zq.is_contiguous() or zq.shape != z.shape):
-        raise L.SelError(f"sel: rvq_step_wire writes a contiguous fp32 zq of shape {tuple(z.shape)}")
-    if rows_per_sample < 1 or rows % rows_per_sample:
-        raise L.SelError(f"sel: rvq_step_wire rows ({rows}) is not a multiple of rows_per_sample ({rows_per_sample})")
+    S, D, K, rows = _quantizer_operands("rvq_step_wire", z, embeds, idx, zq, rows_per_sample)
     _wire_operand("rvq_step_wire", wire, rows, S, K)
     _count_operand("rvq_step_wire", n_active)
     L.call("sel_rvq_step_wire", L.ptr(z), rows, rows_per_sample, D, L.ptr(embeds), S, K, L.ptr(n_active),
@@ -338,32 +354,13 @@ def rvq_lookup_wire_step(wire, codebook, codebooks, out, rows_per_sample=1, mean
     zero.  idx_out (codebooks, rows) int64, when given, receives the flattened
     ids (-1 for such a field).  Nothing is allocated.  Returns out."""
     L.need_device(wire, codebook, out, mean, scale, n_active, idx_out)
-    if codebook.dim() != 2 or codebook.dtype != torch.float32 or not codebook.is_contiguous():
-        raise L.SelError(f"sel: rvq_lookup_wire_step takes a contiguous fp32 (ncodes, D) codebook, got "
-                         f"{codebook.dtype} {tuple(codebook.shape)}")
-    ncodes, D = codebook.shape
-    S = int(codebooks)
-    if S < 1 or ncodes % S or ncodes < S:
-        raise L.SelError(f"sel: rvq_lookup_wire_step: a codebook of {ncodes} rows is not {S} stages of one size")
-    K = ncodes // S
+    S, K, D = _lookup_codebook("rvq_lookup_wire_step", codebook, codebooks)
     if wire is None or wire.dim() != 2:
         raise L.SelError("sel: rvq_lookup_wire_step takes a (rows, frame_bytes) uint8 wire buffer")
     rows = wire.shape[0]
     _wire_operand("rvq_lookup_wire_step", wire, rows, S, K)
-    if out.dtype not in (torch.float32, torch.bfloat16) or not out.is_contiguous() or out.numel() != rows * D:
-        raise L.SelError(f"sel: rvq_lookup_wire_step writes {rows} contiguous fp32 / bf16 rows of {D}, got {out.dtype} "
-                         f"{tuple(out.shape)}")
-    if idx_out is not None and (idx_out.dtype != torch.int64 or not idx_out.is_contiguous()
-                                or tuple(idx_out.shape) != (S, rows)):
-        raise L.SelError(f"sel: rvq_lookup_wire_step writes a contiguous int64 idx_out of shape {(S, rows)}")
-    if (mean is None) != (scale is None):
-        raise L.SelError("sel: rvq_lookup_wire_step takes mean and scale together or not at all")
-    for t in (mean, scale):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != D):
-            raise L.SelError(f"sel: rvq_lookup_wire_step takes contiguous fp32 mean / scale of {D} elements")
-    if rows_per_sample < 1 or rows % rows_per_sample:
-        raise L.SelError(f"sel: rvq_lookup_wire_step rows ({rows}) is not a multiple of rows_per_sample "
-                         f"({rows_per_sample})")
+    _lookup_outputs("rvq_lookup_wire_step", out, rows, D, mean, scale, idx_out, S)
+    _rows_per_sample("rvq_lookup_wire_step", rows, rows_per_sample)
     _count_operand("rvq_lookup_wire_step", n_active)
     L.call("sel_rvq_lookup_wire_step", L.ptr(wire), rows, rows_per_sample, S, K, D, L.ptr(codebook), L.ptr(mean),
            L.ptr(scale), L.ptr(n_active), CO._code(out.dtype), L.ptr(out), L.ptr(idx_out), L.stream())
@@ -401,20 +398,7 @@ def rvq_step_dgram(z, embeds, dgram, rows_per_sample=1, n_active=None, stages=No
     is staged into them.  idx (optional) gets -1 in the stages not run, zq is the
     truncated sum.  Nothing is allocated.  Returns dgram."""
     L.need_device(z, embeds, dgram, idx, n_active, stages, seq, zq)
-    if embeds.dim() != 3 or embeds.dtype != torch.float32 or not embeds.is_contiguous():
-        raise L.SelError(f"sel: rvq_step_dgram takes a contiguous fp32 (S, D, K) stack, got {embeds.dtype} "
-                         f"{tuple(embeds.shape)}")
-    S, D, K = embeds.shape
-    if z.dim() != 2 or z.shape[1] != D or z.dtype != torch.float32 or not z.is_contiguous():
-        raise L.SelError(f"sel: rvq_step_dgram takes contiguous fp32 rows (rows, {D}), got {z.dtype} {tuple(z.shape)}")
-    rows = z.shape[0]
-    if idx is not None and (idx.dtype != torch.int64 or not idx.is_contiguous() or tuple(idx.shape) != (S, rows)):
-        raise L.SelError(f"sel: rvq_step_dgram writes a contiguous int64 idx of shape {(S, rows)}, got {idx.dtype} "
-                         f"{tuple(idx.shape)}")
-    if zq is not None and (zq.dtype != torch.float32 or not zq.is_contiguous() or zq.shape != z.shape):
-        raise L.SelError(f"sel: rvq_step_dgram writes a contiguous fp32 zq of shape {tuple(z.shape)}")
-    if rows_per_sample < 1 or rows % rows_per_sample:
-        raise L.SelError(f"sel: rvq_step_dgram rows ({rows}) is not a multiple of rows_per_sample ({rows_per_sample})")
+    S, D, K, rows = _quantizer_operands("rvq_step_dgram", z, embeds, idx, zq, rows_per_sample)
     B = rows // rows_per_sample
     stride = _dgram_operand("rvq_step_dgram", dgram, B, S, K, rows_per_sample)
     _count_operand("rvq_step_dgram", n_active)
@@ -438,32 +422,14 @@ def rvq_lookup_dgram_step(dgram, codebook, codebooks, out, rows_per_sample=1, me
     B int32 each, DEVICE.  idx_out (codebooks, rows) int64, when given, receives
     the ids summed.  Nothing is allocated.  Returns out."""
     L.need_device(dgram, codebook, out, mean, scale, n_active, slots, lost, hold, idx_out)
-    if codebook.dim() != 2 or codebook.dtype != torch.float32 or not codebook.is_contiguous():
-        raise L.SelError(f"sel: rvq_lookup_dgram_step takes a contiguous fp32 (ncodes, D) codebook, got "
-                         f"{codebook.dtype} {tuple(codebook.shape)}")
-    ncodes, D = codebook.shape
-    S = int(codebooks)
-    if S < 1 or ncodes % S or ncodes < S:
-        raise L.SelError(f"sel: rvq_lookup_dgram_step: a codebook of {ncodes} rows is not {S} stages of one size")
-    K = ncodes // S
-    if rows_per_sample < 1:
-        raise L.SelError(f"sel: rvq_lookup_dgram_step rows_per_sample ({rows_per_sample}) must be positive")
+    S, K, D = _lookup_codebook("rvq_lookup_dgram_step", codebook, codebooks)
     if dgram is None or dgram.dim() != 2:
         raise L.SelError("sel: rvq_lookup_dgram_step takes a (B, stride) uint8 datagram buffer")
     B = dgram.shape[0]
     rows = B * rows_per_sample
+    _rows_per_sample("rvq_lookup_dgram_step", rows, rows_per_sample)       # rows_per_sample < 1
     stride = _dgram_operand("rvq_lookup_dgram_step", dgram, B, S, K, rows_per_sample)
-    if out.dtype not in (torch.float32, torch.bfloat16) or not out.is_contiguous() or out.numel() != rows * D:
-        raise L.SelError(f"sel: rvq_lookup_dgram_step writes {rows} contiguous fp32 / bf16 rows of {D}, got "
-                         f"{out.dtype} {tuple(out.shape)}")
-    if idx_out is not None and (idx_out.dtype != torch.int64 or not idx_out.is_contiguous()
-                                or tuple(idx_out.shape) != (S, rows)):
-        raise L.SelError(f"sel: rvq_lookup_dgram_step writes a contiguous int64 idx_out of shape {(S, rows)}")
-    if (mean is None) != (scale is None):
-        raise L.SelError("sel: rvq_lookup_dgram_step takes mean and scale together or not at all")
-    for t in (mean, scale):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != D):
-            raise L.SelError(f"sel: rvq_lookup_dgram_step takes contiguous fp32 mean / scale of {D} elements")
+    _lookup_outputs("rvq_lookup_dgram_step", out, rows, D, mean, scale, idx_out, S)
     nslots, hold_stride = 0, 0
     if hold is not None:
         from .wire import DatagramFormat

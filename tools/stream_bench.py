@@ -114,6 +114,113 @@ def _stats(v):
     return dict(med=float(np.median(v)), p5=float(np.percentile(v, 5)), p95=float(np.percentile(v, 95)))
 
 
+# ---- what the --pool / --codes / --wire / --datagrams measurements share ------------------------
+def _models(dev, vocoder=False):
+    """The full-width AudioDec generator (seed 93) and, on request, the v1 vocoder."""
+    from models.autoencoder.AudioDec import StreamGenerator as Encoder
+    torch.manual_seed(93)
+    E = Encoder().to(dev).eval()
+    E.quantizer.initial()
+    if not vocoder:
+        return E, None
+    from models.vocoder.HiFiGAN import StreamGenerator as Vocoder
+    from sel import configs
+    return E, Vocoder(**configs.VOCODER_V1).to(dev).eval()
+
+
+def _maker(G, kind, N, chunk, dtype, lookup=None):
+    """-> make(codes=None): a graph object of generator G (AudioDec or vocoder), `kind`
+    = "session" (batch N) or "pool" (capacity N), with `lookup` as its
+    lookup_generator and, given a dict, enable_codes(**codes)."""
+    from sel import streaming as ST
+    vocoder = not hasattr(G, "quantizer")
+    cls = {("session", False): ST.StreamSession, ("pool", False): ST.StreamPool,
+           ("session", True): ST.VocoderSession, ("pool", True): ST.VocoderPool}[kind, vocoder]
+
+    def make(codes=None):
+        o = cls(G, N, chunk // 300 if vocoder else chunk, graph=True, dtype=dtype)
+        if lookup is not None:
+            o.lookup_generator = lookup
+        if codes is not None:
+            o.enable_codes(**codes)
+        return o
+    return make
+
+
+def _open_all(objs, N):
+    """Every slot of every pool among objs, in the same order -> the leading arguments of a tick"""
+    lists = [[o.open() for _ in range(N)] for o in objs if hasattr(o, "table")]
+    assert all(sl == lists[0] for sl in lists)
+    return (lists[0],) if lists else ()
+
+
+def _measure(paths, hops, warmup, dev):
+    """{name: fn}, the paths running alternating hop by hop -> {name: {"host": stats, "gpu": stats}}"""
+    stream = torch.cuda.current_stream(dev)
+    rec = {p: dict(host=[], gpu=[]) for p in paths}
+    for hop in range(warmup + hops):
+        for p, fn in paths.items():
+            _, h, g = _timed(fn, stream)
+            if hop >= warmup:
+                rec[p]["host"].append(h)
+                rec[p]["gpu"].append(g)
+    return {p: {k: _stats(v) for k, v in r.items()} for p, r in rec.items()}
+
+
+def _pairs(paths, hops, warmup, dev):
+    """{half: (old fn, new fn)} -> {half: {"old" / "new": {"host": stats, "gpu": stats}}}"""
+    res = _measure({(h, p): fn for h, fns in paths.items() for p, fn in zip(("old", "new"), fns)}, hops, warmup, dev)
+    return {h: {p: res[h, p] for p in ("old", "new")} for h in paths}
+
+
+def _head(dtype, N, chunk, hops, **first):
+    return dict(**first, dtype=str(dtype).replace("torch.", ""), streams=N, chunk=chunk, hops=hops)
+
+
+def _sweep(a, configs, run):
+    """run(dtype, *config) for every --dtypes entry and config, each result printed as it comes"""
+    results = []
+    for dt in a.dtypes:
+        for cfg in configs:
+            results.append(run(getattr(torch, dt), *cfg))
+            print(json.dumps(results[-1]), flush=True)
+    return results
+
+
+def _kinds(a):
+    return (("session", 1), ("session", a.streams), ("pool", a.streams))
+
+
+def _cell(s):
+    return f"{s['med']:.3f} ({s['p5']:.3f}-{s['p95']:.3f})"
+
+
+def _object(r):
+    return f"{r['kind']} B={r['streams']}" if r["kind"] == "session" else f"pool {r['streams']} of {r['streams']}"
+
+
+def _verdict(o, n, faster=False, names=("old", "new")):
+    """Host stats of two paths -> the acceptance arithmetic: the first minus the
+    second against the wider 5-95 % band; `faster`: must win by more than the
+    band, else: must be no slower by more than it."""
+    gain = o["med"] - n["med"]
+    spread = max(o["p95"] - o["p5"], n["p95"] - n["p5"])
+    met = gain > spread if faster else gain >= -spread
+    return (f"{names[0]} {o['med']:.3f} ms - {names[1]} {n['med']:.3f} ms = {gain:.3f} ms vs 5-95% band "
+            f"{spread:.3f} ms: {'MET' if met else 'NOT MET'}")
+
+
+def _write(out, default, results, lines, verdicts=None):
+    """<out>.json (every figure) and <out>.md (the table, then the verdict lines)"""
+    out = out or os.path.join(REPO, "profiles", default)
+    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    with open(out + ".json", "w") as f:
+        json.dump(results, f, indent=1)
+    with open(out + ".md", "w") as f:
+        f.write("\n".join(lines + ([""] + verdicts if verdicts is not None else [])) + "\n")
+    print("\n".join(lines + (verdicts or [])))
+
+
 def run_config(dtype, B, chunk, hops, warmup, rate, dev):
     from models.autoencoder.AudioDec import StreamGenerator
     from sel import convops as CO
@@ -208,57 +315,6 @@ def run_vocoder_config(decoder, dtype, B, chunk, hops, warmup, rate, dev):
                 chunk_ms=dur_ms, paths=out)
 
 
-def run_pool_config(half, dtype, N, active, chunk, hops, warmup, dev):
-    """One tick of N independent streams, `half` = "tx" (AudioDec encode +
-    quantize) or "rx_v1" (lookup + v1 vocoder decode), at full width."""
-    from models.autoencoder.AudioDec import StreamGenerator as Encoder
-    from models.vocoder.HiFiGAN import StreamGenerator as Vocoder
-    from sel import configs
-    from sel.streaming import StreamPool, StreamSession, VocoderPool, VocoderSession
-    torch.manual_seed(93)
-    E = Encoder().to(dev).eval()
-    E.quantizer.initial()
-    L = chunk // 300
-    x = 0.1 * torch.randn(N, 1, chunk, generator=torch.Generator().manual_seed(1)).to(dev)
-    xs = [x[i:i + 1].contiguous() for i in range(N)]
-    if half == "tx":
-        solo = [StreamSession(E, 1, chunk, graph=True, dtype=dtype) for _ in range(N)]
-        lock = StreamSession(E, N, chunk, graph=True, dtype=dtype)
-        pool = StreamPool(E, N, chunk, graph=True, dtype=dtype)
-        paths = {"solo": lambda: [S.quantize(S.encode(xi)) for S, xi in zip(solo, xs)],
-                 "lockstep": lambda: lock.quantize(lock.encode(x)),
-                 "pool": lambda: pool.quantize(pool.encode(all_slots, x)),
-                 "pool_k": lambda: pool.quantize(pool.encode(some_slots, x_some))}
-    else:
-        V = Vocoder(**configs.VOCODER_V1).to(dev).eval()
-        idx = E.quantize(E.encode(x))                   # (codebooks, N, frames)
-        idxs = [idx[:, i].contiguous() for i in range(N)]
-        solo = [VocoderSession(V, 1, L, graph=True, dtype=dtype) for _ in range(N)]
-        lock = VocoderSession(V, N, L, graph=True, dtype=dtype)
-        pool = VocoderPool(V, N, L, graph=True, dtype=dtype)
-        for S in solo + [lock, pool]:
-            S.lookup_generator = E
-        paths = {"solo": lambda: [S.decode(S.lookup(i)) for S, i in zip(solo, idxs)],
-                 "lockstep": lambda: lock.decode(lock.lookup(idx)),
-                 "pool": lambda: pool.decode(all_slots, pool.lookup(idx)),
-                 "pool_k": lambda: pool.decode(some_slots, pool.lookup(idx_some))}
-    all_slots = [pool.open() for _ in range(N)]
-    some_slots = all_slots[::N // active][:active]
-    x_some = x[some_slots].contiguous()
-    if half != "tx":
-        idx_some = idx[:, some_slots].contiguous()
-    stream = torch.cuda.current_stream(dev)
-    rec = {p: dict(host=[], gpu=[]) for p in paths}
-    for hop in range(warmup + hops):
-        for path, fn in paths.items():
-            _, h, g = _timed(fn, stream)
-            if hop >= warmup:
-                rec[path]["host"].append(h)
-                rec[path]["gpu"].append(g)
-    return dict(half=half, dtype=str(dtype).replace("torch.", ""), streams=N, active=active, chunk=chunk, hops=hops,
-                paths={p: {k: _stats(v) for k, v in r.items()} for p, r in rec.items()})
-
-
 class _no_state_copy:
     """Inside the block a session's or a pool's launch list ends before its
     commit / copy_slots launch, so a graph captured there lacks that node.  For
@@ -281,64 +337,64 @@ def _graph_half(obj, half):
     return obj._enc if half == "tx" else obj._dec
 
 
+def run_pool_config(half, dtype, N, active, chunk, hops, warmup, dev):
+    """One tick of N independent streams, `half` = "tx" (AudioDec encode +
+    quantize) or "rx_v1" (lookup + v1 vocoder decode), at full width."""
+    E, V = _models(dev, vocoder=half != "tx")
+    x = 0.1 * torch.randn(N, 1, chunk, generator=torch.Generator().manual_seed(1)).to(dev)
+    G = E if half == "tx" else V
+    solo = [_maker(G, "session", 1, chunk, dtype, E)() for _ in range(N)]
+    lock, pool = _maker(G, "session", N, chunk, dtype, E)(), _maker(G, "pool", N, chunk, dtype, E)()
+    all_slots, = _open_all([pool], N)
+    some_slots = all_slots[::N // active][:active]
+    if half == "tx":
+        xs, x_some = [x[i:i + 1].contiguous() for i in range(N)], x[some_slots].contiguous()
+        paths = {"solo": lambda: [S.quantize(S.encode(xi)) for S, xi in zip(solo, xs)],
+                 "lockstep": lambda: lock.quantize(lock.encode(x)),
+                 "pool": lambda: pool.quantize(pool.encode(all_slots, x)),
+                 "pool_k": lambda: pool.quantize(pool.encode(some_slots, x_some))}
+    else:
+        idx = E.quantize(E.encode(x))                   # (codebooks, N, frames)
+        idxs, idx_some = [idx[:, i].contiguous() for i in range(N)], idx[:, some_slots].contiguous()
+        paths = {"solo": lambda: [S.decode(S.lookup(i)) for S, i in zip(solo, idxs)],
+                 "lockstep": lambda: lock.decode(lock.lookup(idx)),
+                 "pool": lambda: pool.decode(all_slots, pool.lookup(idx)),
+                 "pool_k": lambda: pool.decode(some_slots, pool.lookup(idx_some))}
+    return dict(half=half, dtype=str(dtype).replace("torch.", ""), streams=N, active=active, chunk=chunk, hops=hops,
+                paths=_measure(paths, hops, warmup, dev))
+
+
 def run_attribution_config(half, dtype, N, chunk, hops, warmup, dev):
     """Where the pool's time over the lockstep session goes at N of N active
     (`half` as run_pool_config).  The inputs are fixed, so the replays alone
     compute the same hop every time."""
-    from models.autoencoder.AudioDec import StreamGenerator as Encoder
-    from models.vocoder.HiFiGAN import StreamGenerator as Vocoder
-    from sel import configs
-    from sel.streaming import StreamPool, StreamSession, VocoderPool, VocoderSession
-    torch.manual_seed(93)
-    E = Encoder().to(dev).eval()
-    E.quantizer.initial()
+    E, V = _models(dev, vocoder=half != "tx")
     if half == "tx":
         inp = 0.1 * torch.randn(N, 1, chunk, generator=torch.Generator().manual_seed(1)).to(dev)
-
-        def build():
-            return (StreamSession(E, N, chunk, graph=True, dtype=dtype),
-                    StreamPool(E, N, chunk, graph=True, dtype=dtype))
-
-        def full(obj, *slots):
-            return obj.encode(*slots, inp)
     else:
-        V = Vocoder(**configs.VOCODER_V1).to(dev).eval()
         inp = torch.randn(N, chunk // 300, 64, generator=torch.Generator().manual_seed(2)).to(dev)
 
-        def build():
-            return (VocoderSession(V, N, chunk // 300, graph=True, dtype=dtype),
-                    VocoderPool(V, N, chunk // 300, graph=True, dtype=dtype))
+    def build():
+        return [_maker(E if half == "tx" else V, kind, N, chunk, dtype)() for kind in ("session", "pool")]
 
-        def full(obj, *slots):
-            return obj.decode(*slots, inp)
+    def full(obj, *slots):
+        return obj.encode(*slots, inp) if half == "tx" else obj.decode(*slots, inp)
+
     lock, pool = build()
     with _no_state_copy():
         lock0, pool0 = build()
+    slots, = _open_all([pool, pool0], N)
     for p in (pool, pool0):
-        slots = [p.open() for _ in range(N)]
         full(p, slots)                  # leaves the full list staged for the bare replays
     hl, hl0, hp, hp0 = (_graph_half(o, half) for o in (lock, lock0, pool, pool0))
     paths = {"lock_replay_no_commit": hl0.run, "lock_replay": hl.run, "pool_replay_no_copy": hp0.run,
              "pool_replay": hp.run, "lock_full": lambda: full(lock), "pool_full": lambda: full(pool, slots)}
-    stream = torch.cuda.current_stream(dev)
-    rec = {p: dict(host=[], gpu=[]) for p in paths}
-    for hop in range(warmup + hops):
-        for path, fn in paths.items():
-            _, h, g = _timed(fn, stream)
-            if hop >= warmup:
-                rec[path]["host"].append(h)
-                rec[path]["gpu"].append(g)
-    return dict(half=half, dtype=str(dtype).replace("torch.", ""), streams=N, chunk=chunk, hops=hops,
-                paths={p: {k: _stats(v) for k, v in r.items()} for p, r in rec.items()})
+    return dict(_head(dtype, N, chunk, hops, half=half), paths=_measure(paths, hops, warmup, dev))
 
 
 def main_attribution(a, dev):
-    results = []
-    for dt in a.dtypes:
-        for half in ("tx", "rx_v1"):
-            r = run_attribution_config(half, getattr(torch, dt), a.streams, 300, a.hops, a.warmup, dev)
-            results.append(r)
-            print(json.dumps(r), flush=True)
+    results = _sweep(a, (("tx",), ("rx_v1",)),
+                     lambda dt, half: run_attribution_config(half, dt, a.streams, 300, a.hops, a.warmup, dev))
     label = {"lock_replay": "lockstep replay", "lock_replay_no_commit": "... without its commit launch",
              "pool_replay_no_copy": "pool replay without its copy launch", "pool_replay": "pool replay",
              "pool_full": "pool full call (staging, input fill, replay)", "lock_full": "lockstep full call"}
@@ -356,48 +412,42 @@ def main_attribution(a, dev):
         r["parts_host_ms"] = parts
         lines.append(f"{r['half']} {r['dtype']}: indirection {parts['indirection']:.3f} ms, staging "
                      f"{parts['staging']:.3f} ms, copy launch {parts['copy']:.3f} ms (commit {parts['commit']:.3f} ms)")
-    out = a.out or os.path.join(REPO, "profiles", "stream_pool_attribution")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out + ".json", "w") as f:
-        json.dump(results, f, indent=1)
-    with open(out + ".md", "w") as f:
-        f.write("\n".join(lines) + "\n")
-    print("\n".join(lines))
+    _write(a.out, "stream_pool_attribution", results, lines)
 
 
 def main_pool(a, dev):
-    results = []
-    for dt in a.dtypes:
-        for half in ("tx", "rx_v1"):
-            r = run_pool_config(half, getattr(torch, dt), a.streams, a.active, 300, a.hops, a.warmup, dev)
-            results.append(r)
-            print(json.dumps(r), flush=True)
+    results = _sweep(a, (("tx",), ("rx_v1",)),
+                     lambda dt, half: run_pool_config(half, dt, a.streams, a.active, 300, a.hops, a.warmup, dev))
     label = {"solo": "(a) {n} solo batch=1 sessions", "lockstep": "(b) lockstep batch={n} session",
              "pool": "(c) pool, {n} of {n} active", "pool_k": "(d) pool, {k} of {n} active"}
     lines = ["| half | dtype | path | host ms med (p5-p95) | GPU ms med (p5-p95) |", "|---|---|---|---|---|"]
     verdicts = []
     for r in results:
         for path, lab in label.items():
-            h, g = r["paths"][path]["host"], r["paths"][path]["gpu"]
             lines.append(f"| {r['half']} | {r['dtype']} | {lab.format(n=r['streams'], k=r['active'])} | "
-                         f"{h['med']:.3f} ({h['p5']:.3f}-{h['p95']:.3f}) | "
-                         f"{g['med']:.3f} ({g['p5']:.3f}-{g['p95']:.3f}) |")
+                         f"{_cell(r['paths'][path]['host'])} | {_cell(r['paths'][path]['gpu'])} |")
         pa = {k: v["host"] for k, v in r["paths"].items()}
-        gain = pa["solo"]["med"] - pa["pool"]["med"]
-        spread = max(pa["solo"]["p95"] - pa["solo"]["p5"], pa["pool"]["p95"] - pa["pool"]["p5"])
-        verdicts.append(f"acceptance {r['half']} {r['dtype']}: solo {pa['solo']['med']:.3f} ms - pool "
-                        f"{pa['pool']['med']:.3f} ms = {gain:.3f} ms vs 5-95% band {spread:.3f} ms: "
-                        f"{'MET' if gain > spread else 'NOT MET'}; (c)/(b) = "
+        verdicts.append(f"acceptance {r['half']} {r['dtype']}: "
+                        f"{_verdict(pa['solo'], pa['pool'], True, ('solo', 'pool'))}; (c)/(b) = "
                         f"{pa['pool']['med'] / pa['lockstep']['med']:.3f}, (d)/(c) = "
                         f"{pa['pool_k']['med'] / pa['pool']['med']:.3f}, (a)/(c) = "
                         f"{pa['solo']['med'] / pa['pool']['med']:.2f}")
-    out = a.out or os.path.join(REPO, "profiles", "stream_pool_bench")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out + ".json", "w") as f:
-        json.dump(results, f, indent=1)
-    with open(out + ".md", "w") as f:
-        f.write("\n".join(lines + [""] + verdicts) + "\n")
-    print("\n".join(lines + verdicts))
+    _write(a.out, "stream_pool_bench", results, lines, verdicts)
+
+
+def _codec_objects(kind, dtype, N, chunk, dev, old, new, copies=1):
+    """The models and inputs of --codes / --wire: per receiver ("ae": the AudioDec
+    decoder, "v1": the vocoder) `copies` pairs of objects of `kind` with
+    enable_codes(**old) (None: not enabled) and enable_codes(**new), all pools'
+    slots open -> (objects by receiver, the leading arguments of a tick, x, idx
+    as the objects' quantize returns it)"""
+    E, V = _models(dev, vocoder=True)
+    x = 0.1 * torch.randn(N, 1, chunk, generator=torch.Generator().manual_seed(1)).to(dev)
+    idx = E.quantize(E.encode(x))
+    objs = {name: [_maker(G, kind, N, chunk, dtype, E)(codes) for codes in (old, new) * copies]
+            for name, G in (("ae", E), ("v1", V))}
+    idx = idx.view(idx.shape[0], N, chunk // 300)
+    return objs, _open_all(objs["ae"] + objs["v1"], N), x, idx.squeeze(1) if kind == "session" and N == 1 else idx
 
 
 def run_codes_config(kind, dtype, N, chunk, hops, warmup, dev):
@@ -405,94 +455,39 @@ def run_codes_config(kind, dtype, N, chunk, hops, warmup, dev):
     AudioDec decoder and with the v1 vocoder, `kind` = "session" (batch N) or
     "pool" (N of N slots active), at full width.  The old and the new path run
     on separate objects fed the same input, so each advances its own state."""
-    from models.autoencoder.AudioDec import StreamGenerator as Encoder
-    from models.vocoder.HiFiGAN import StreamGenerator as Vocoder
-    from sel import configs
-    from sel.streaming import StreamPool, StreamSession, VocoderPool, VocoderSession
-    torch.manual_seed(93)
-    E = Encoder().to(dev).eval()
-    E.quantizer.initial()
-    V = Vocoder(**configs.VOCODER_V1).to(dev).eval()
-    L = chunk // 300
-    x = 0.1 * torch.randn(N, 1, chunk, generator=torch.Generator().manual_seed(1)).to(dev)
-    idx = E.quantize(E.encode(x))
-    pool = kind == "pool"
-    if pool:
-        idx = idx.view(idx.shape[0], N, L)
-
-    def make_ae():
-        return StreamPool(E, N, chunk, graph=True, dtype=dtype) if pool else StreamSession(E, N, chunk, graph=True,
-                                                                                           dtype=dtype)
-
-    def make_v1():
-        return VocoderPool(V, N, L, graph=True, dtype=dtype) if pool else VocoderSession(V, N, L, graph=True,
-                                                                                         dtype=dtype)
-
-    objs = {}
-    for name, make in (("ae", make_ae), ("v1", make_v1)):
-        old, new = make(), make()
-        for o in (old, new):
-            o.lookup_generator = E
-        new.enable_codes()
-        objs[name] = (old, new)
-    sl = ()
-    if pool:
-        for old, new in objs.values():
-            sl = ([old.open() for _ in range(N)],)
-            assert [new.open() for _ in range(N)] == sl[0]
-    ae_old, ae_new = objs["ae"]
-    v1_old, v1_new = objs["v1"]
+    objs, sl, x, idx = _codec_objects(kind, dtype, N, chunk, dev, None, {})
+    (ae_old, ae_new), (v1_old, v1_new) = objs["ae"], objs["v1"]
     paths = {"tx": (lambda: ae_old.quantize(ae_old.encode(*sl, x)), lambda: ae_new.transmit(*sl, x)),
              "rx": (lambda: ae_old.decode(*sl, ae_old.lookup(idx)), lambda: ae_new.receive(*sl, idx)),
              "rx_v1": (lambda: v1_old.decode(*sl, v1_old.lookup(idx)), lambda: v1_new.receive(*sl, idx))}
-    stream = torch.cuda.current_stream(dev)
-    rec = {h: {p: dict(host=[], gpu=[]) for p in ("old", "new")} for h in paths}
-    for hop in range(warmup + hops):
-        for half, fns in paths.items():
-            for p, fn in zip(("old", "new"), fns):
-                _, h, g = _timed(fn, stream)
-                if hop >= warmup:
-                    rec[half][p]["host"].append(h)
-                    rec[half][p]["gpu"].append(g)
-    return dict(kind=kind, dtype=str(dtype).replace("torch.", ""), streams=N, chunk=chunk, hops=hops,
-                halves={h: {p: {k: _stats(v) for k, v in r.items()} for p, r in d.items()} for h, d in rec.items()})
+    return dict(_head(dtype, N, chunk, hops, kind=kind), halves=_pairs(paths, hops, warmup, dev))
+
+
+def _pair_table(results, label, faster=lambda r, half: False, recorded=()):
+    """The table and the verdict lines of --codes / --wire: per object and half the old row, the new row"""
+    lines = ["| dtype | object | half | path | host ms med (p5-p95) | GPU ms med (p5-p95) |",
+             "|---|---|---|---|---|---|"]
+    verdicts = []
+    for r in results:
+        for half, d in r["halves"].items():
+            for p in ("old", "new"):
+                lines.append(f"| {r['dtype']} | {_object(r)} | {half} | {label[half, p]} | {_cell(d[p]['host'])} | "
+                             f"{_cell(d[p]['gpu'])} |")
+            if half not in recorded:
+                win = faster(r, half)                    # must win; the rest: no slower
+                verdicts.append(f"acceptance {r['dtype']} {_object(r)} {half} ({'faster' if win else 'no slower'}): "
+                                f"{_verdict(d['old']['host'], d['new']['host'], win)}")
+    return lines, verdicts
 
 
 def main_codes(a, dev):
-    results = []
-    for dt in a.dtypes:
-        for kind, N in (("session", 1), ("session", a.streams), ("pool", a.streams)):
-            r = run_codes_config(kind, getattr(torch, dt), N, 300, a.hops, a.warmup, dev)
-            results.append(r)
-            print(json.dumps(r), flush=True)
+    results = _sweep(a, _kinds(a), lambda dt, kind, N: run_codes_config(kind, dt, N, 300, a.hops, a.warmup, dev))
     label = {("tx", "old"): "(a) encode replay + quantize", ("tx", "new"): "(b) transmit",
              ("rx", "old"): "(a') lookup + decode replay", ("rx", "new"): "(b') receive",
              ("rx_v1", "old"): "(a') lookup + v1 decode replay", ("rx_v1", "new"): "(b') v1 receive"}
-    lines = ["| dtype | object | half | path | host ms med (p5-p95) | GPU ms med (p5-p95) |", "|---|---|---|---|---|---|"]
-    verdicts = []
-    for r in results:
-        what = f"{r['kind']} B={r['streams']}" if r["kind"] == "session" else f"pool {r['streams']} of {r['streams']}"
-        for half, d in r["halves"].items():
-            for p in ("old", "new"):
-                h, g = d[p]["host"], d[p]["gpu"]
-                lines.append(f"| {r['dtype']} | {what} | {half} | {label[half, p]} | "
-                             f"{h['med']:.3f} ({h['p5']:.3f}-{h['p95']:.3f}) | "
-                             f"{g['med']:.3f} ({g['p5']:.3f}-{g['p95']:.3f}) |")
-            o, n = d["old"]["host"], d["new"]["host"]
-            gain = o["med"] - n["med"]
-            spread = max(o["p95"] - o["p5"], n["p95"] - n["p5"])
-            faster = half == "tx" and r["kind"] == "session" and r["streams"] == 1     # must win; the rest: no slower
-            met = gain > spread if faster else gain >= -spread
-            verdicts.append(f"acceptance {r['dtype']} {what} {half} ({'faster' if faster else 'no slower'}): old "
-                            f"{o['med']:.3f} ms - new {n['med']:.3f} ms = {gain:.3f} ms vs 5-95% band {spread:.3f} ms: "
-                            f"{'MET' if met else 'NOT MET'}")
-    out = a.out or os.path.join(REPO, "profiles", "stream_codes_bench")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out + ".json", "w") as f:
-        json.dump(results, f, indent=1)
-    with open(out + ".md", "w") as f:
-        f.write("\n".join(lines + [""] + verdicts) + "\n")
-    print("\n".join(lines + verdicts))
+    lines, verdicts = _pair_table(results, label, lambda r, half: half == "tx" and r["kind"] == "session"
+                                  and r["streams"] == 1)
+    _write(a.out, "stream_codes_bench", results, lines, verdicts)
 
 
 def run_wire_config(kind, dtype, N, chunk, hops, warmup, dev):
@@ -500,42 +495,7 @@ def run_wire_config(kind, dtype, N, chunk, hops, warmup, dev):
     and v1 vocoder), `kind` = "session" (batch N) or "pool" (N of N slots
     active), at full width, old and new on separate objects as run_codes_config;
     tx_host is the transmitter's hop with its result copied to the host."""
-    from models.autoencoder.AudioDec import StreamGenerator as Encoder
-    from models.vocoder.HiFiGAN import StreamGenerator as Vocoder
-    from sel import configs
-    from sel.streaming import StreamPool, StreamSession, VocoderPool, VocoderSession
-    torch.manual_seed(93)
-    E = Encoder().to(dev).eval()
-    E.quantizer.initial()
-    V = Vocoder(**configs.VOCODER_V1).to(dev).eval()
-    L = chunk // 300
-    x = 0.1 * torch.randn(N, 1, chunk, generator=torch.Generator().manual_seed(1)).to(dev)
-    idx = E.quantize(E.encode(x))
-    pool = kind == "pool"
-    idx = idx.view(idx.shape[0], N, L)
-    if not pool and N == 1:
-        idx = idx.squeeze(1)
-
-    def make_ae():
-        return StreamPool(E, N, chunk, graph=True, dtype=dtype) if pool else StreamSession(E, N, chunk, graph=True,
-                                                                                           dtype=dtype)
-
-    def make_v1():
-        return VocoderPool(V, N, L, graph=True, dtype=dtype) if pool else VocoderSession(V, N, L, graph=True,
-                                                                                         dtype=dtype)
-
-    objs = {}
-    for name, make in (("ae", make_ae), ("v1", make_v1)):
-        old, new, old_h, new_h = make(), make(), make(), make()
-        for o, wire in ((old, False), (new, True), (old_h, False), (new_h, True)):
-            o.lookup_generator = E
-            o.enable_codes(wire=wire)
-        objs[name] = (old, new, old_h, new_h)
-    sl = ()
-    if pool:
-        for group in objs.values():
-            for o in group:
-                sl = ([o.open() for _ in range(N)],)
+    objs, sl, x, idx = _codec_objects(kind, dtype, N, chunk, dev, dict(wire=False), dict(wire=True), copies=2)
     ae_old, ae_new, ae_old_h, ae_new_h = objs["ae"]
     v1_old, v1_new = objs["v1"][:2]
     packets = ae_new.wire.pack(idx.cpu()).to(dev)
@@ -543,62 +503,25 @@ def run_wire_config(kind, dtype, N, chunk, hops, warmup, dev):
              "rx": (lambda: ae_old.receive(*sl, idx), lambda: ae_new.receive_packets(*sl, packets)),
              "rx_v1": (lambda: v1_old.receive(*sl, idx), lambda: v1_new.receive_packets(*sl, packets)),
              "tx_host": (lambda: ae_old_h.transmit(*sl, x).cpu(), lambda: ae_new_h.transmit_packets(*sl, x).cpu())}
-    stream = torch.cuda.current_stream(dev)
-    rec = {h: {p: dict(host=[], gpu=[]) for p in ("old", "new")} for h in paths}
-    for hop in range(warmup + hops):
-        for half, fns in paths.items():
-            for p, fn in zip(("old", "new"), fns):
-                _, h, g = _timed(fn, stream)
-                if hop >= warmup:
-                    rec[half][p]["host"].append(h)
-                    rec[half][p]["gpu"].append(g)
     w = ae_new.wire
-    return dict(kind=kind, dtype=str(dtype).replace("torch.", ""), streams=N, chunk=chunk, hops=hops,
+    return dict(_head(dtype, N, chunk, hops, kind=kind),
                 wire=dict(version=w.version, bits=w.bits, frame_bytes=w.frame_bytes, packet_bytes=w.packet_bytes,
                           index_bytes=8 * w.codebooks * w.frames),
-                halves={h: {p: {k: _stats(v) for k, v in r.items()} for p, r in d.items()} for h, d in rec.items()})
+                halves=_pairs(paths, hops, warmup, dev))
 
 
 def main_wire(a, dev):
-    results = []
-    for dt in a.dtypes:
-        for kind, N in (("session", 1), ("session", a.streams), ("pool", a.streams)):
-            r = run_wire_config(kind, getattr(torch, dt), N, 300, a.hops, a.warmup, dev)
-            results.append(r)
-            print(json.dumps(r), flush=True)
+    results = _sweep(a, _kinds(a), lambda dt, kind, N: run_wire_config(kind, dt, N, 300, a.hops, a.warmup, dev))
     label = {("tx", "old"): "transmit", ("tx", "new"): "transmit_packets",
              ("rx", "old"): "receive", ("rx", "new"): "receive_packets",
              ("rx_v1", "old"): "v1 receive", ("rx_v1", "new"): "v1 receive_packets",
              ("tx_host", "old"): "transmit + idx.cpu() (recorded only)",
              ("tx_host", "new"): "transmit_packets + .cpu() (recorded only)"}
-    lines = ["| dtype | object | half | path | host ms med (p5-p95) | GPU ms med (p5-p95) |", "|---|---|---|---|---|---|"]
-    verdicts = []
-    for r in results:
-        what = f"{r['kind']} B={r['streams']}" if r["kind"] == "session" else f"pool {r['streams']} of {r['streams']}"
-        for half, d in r["halves"].items():
-            for p in ("old", "new"):
-                h, g = d[p]["host"], d[p]["gpu"]
-                lines.append(f"| {r['dtype']} | {what} | {half} | {label[half, p]} | "
-                             f"{h['med']:.3f} ({h['p5']:.3f}-{h['p95']:.3f}) | "
-                             f"{g['med']:.3f} ({g['p5']:.3f}-{g['p95']:.3f}) |")
-            if half == "tx_host":
-                continue
-            o, n = d["old"]["host"], d["new"]["host"]
-            gain = o["med"] - n["med"]
-            spread = max(o["p95"] - o["p5"], n["p95"] - n["p5"])
-            verdicts.append(f"acceptance {r['dtype']} {what} {half} (no slower): old {o['med']:.3f} ms - new "
-                            f"{n['med']:.3f} ms = {gain:.3f} ms vs 5-95% band {spread:.3f} ms: "
-                            f"{'MET' if gain >= -spread else 'NOT MET'}")
+    lines, verdicts = _pair_table(results, label, recorded=("tx_host",))
     w = results[0]["wire"]
     verdicts.append(f"wire v{w['version']}: {w['bits']} bits per field, {w['frame_bytes']} bytes per frame against "
                     f"{w['index_bytes']} bytes of int64 indices")
-    out = a.out or os.path.join(REPO, "profiles", "stream_wire_bench")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out + ".json", "w") as f:
-        json.dump(results, f, indent=1)
-    with open(out + ".md", "w") as f:
-        f.write("\n".join(lines + [""] + verdicts) + "\n")
-    print("\n".join(lines + verdicts))
+    _write(a.out, "stream_wire_bench", results, lines, verdicts)
 
 
 def run_dgram_config(kind, dtype, N, chunk, hops, warmup, dev):
@@ -607,25 +530,15 @@ def run_dgram_config(kind, dtype, N, chunk, hops, warmup, dev):
     receive_datagrams with nothing lost, and a tick with every stream lost;
     `kind` = "session" (batch N) or "pool" (N of N slots active), full width,
     separate objects, the paths alternating hop by hop."""
-    from models.autoencoder.AudioDec import StreamGenerator as Encoder
-    from sel.streaming import StreamPool, StreamSession
-    torch.manual_seed(93)
-    E = Encoder().to(dev).eval()
-    E.quantizer.initial()
+    E, _ = _models(dev)
     x = 0.1 * torch.randn(N, 1, chunk, generator=torch.Generator().manual_seed(1)).to(dev)
-    pool = kind == "pool"
-
-    def make(**kw):
-        o = StreamPool(E, N, chunk, graph=True, dtype=dtype) if pool else StreamSession(E, N, chunk, graph=True,
-                                                                                        dtype=dtype)
-        o.enable_codes(**kw)
-        return o, (([o.open() for _ in range(N)],) if pool else ())
-
+    make = _maker(E, kind, N, chunk, dtype)
     S = len(E.quantizer.codebook.layers)
     budgets = [S] + [b for b in (4, 2, 1) if b < S]
-    (tx_old, sl), (rx_old, _), (rx_new, _), (rx_lost, _) = (make(wire=True), make(wire=True), make(datagrams=True),
-                                                           make(datagrams=True))
-    tx_new = {b: make(datagrams=True)[0] for b in budgets}
+    tx_old, rx_old = make(dict(wire=True)), make(dict(wire=True))
+    rx_new, rx_lost = make(dict(datagrams=True)), make(dict(datagrams=True))
+    tx_new = {b: make(dict(datagrams=True)) for b in budgets}
+    sl = _open_all([tx_old, rx_old, rx_new, rx_lost] + list(tx_new.values()), N)
     packets = tx_old.transmit_packets(*sl, x).clone()
     dgrams = tx_new[S].transmit_datagrams(*sl, x).clone()
     gone = [1] * N
@@ -634,29 +547,16 @@ def run_dgram_config(kind, dtype, N, chunk, hops, warmup, dev):
              "rx_all_lost": lambda: rx_lost.receive_datagrams(*sl, dgrams, gone)}
     for b in budgets:
         paths[f"tx_dgram_s{b}"] = functools.partial(lambda o, b: o.transmit_datagrams(*sl, x, b), tx_new[b], b)
-    stream = torch.cuda.current_stream(dev)
-    rec = {p: dict(host=[], gpu=[]) for p in paths}
-    for hop in range(warmup + hops):
-        for p, fn in paths.items():
-            _, h, g = _timed(fn, stream)
-            if hop >= warmup:
-                rec[p]["host"].append(h)
-                rec[p]["gpu"].append(g)
     f = rx_new.datagram
-    return dict(kind=kind, dtype=str(dtype).replace("torch.", ""), streams=N, chunk=chunk, hops=hops, budgets=budgets,
+    return dict(_head(dtype, N, chunk, hops, kind=kind), budgets=budgets,
                 datagram=dict(version=f.version, bits=f.bits, stride=f.stride,
                               bytes={b: f.datagram_bytes(b) for b in budgets},
                               kbit_per_s={b: f.bitrate(48000, chunk, b) / 1e3 for b in budgets}),
-                paths={p: {k: _stats(v) for k, v in r.items()} for p, r in rec.items()})
+                paths=_measure(paths, hops, warmup, dev))
 
 
 def main_dgram(a, dev):
-    results = []
-    for dt in a.dtypes:
-        for kind, N in (("session", 1), ("session", a.streams), ("pool", a.streams)):
-            r = run_dgram_config(kind, getattr(torch, dt), N, 300, a.hops, a.warmup, dev)
-            results.append(r)
-            print(json.dumps(r), flush=True)
+    results = _sweep(a, _kinds(a), lambda dt, kind, N: run_dgram_config(kind, dt, N, 300, a.hops, a.warmup, dev))
     S = results[0]["budgets"][0]
     order = ["tx"] + [f"tx_dgram_s{b}" for b in results[0]["budgets"]] + ["rx", "rx_dgram", "rx_all_lost"]
     label = {"tx": "transmit_packets", "rx": "receive_packets", "rx_dgram": "receive_datagrams, none lost",
@@ -665,62 +565,39 @@ def main_dgram(a, dev):
     lines = ["| dtype | object | path | host ms med (p5-p95) | GPU ms med (p5-p95) |", "|---|---|---|---|---|"]
     verdicts = []
     for r in results:
-        what = f"{r['kind']} B={r['streams']}" if r["kind"] == "session" else f"pool {r['streams']} of {r['streams']}"
         for p in order:
-            h, g = r["paths"][p]["host"], r["paths"][p]["gpu"]
-            lines.append(f"| {r['dtype']} | {what} | {label[p]} | {h['med']:.3f} ({h['p5']:.3f}-{h['p95']:.3f}) | "
-                         f"{g['med']:.3f} ({g['p5']:.3f}-{g['p95']:.3f}) |")
+            lines.append(f"| {r['dtype']} | {_object(r)} | {label[p]} | {_cell(r['paths'][p]['host'])} | "
+                         f"{_cell(r['paths'][p]['gpu'])} |")
         for old, new in (("tx", f"tx_dgram_s{S}"), ("rx", "rx_dgram")):
-            o, n = r["paths"][old]["host"], r["paths"][new]["host"]
-            gain = o["med"] - n["med"]
-            spread = max(o["p95"] - o["p5"], n["p95"] - n["p5"])
-            verdicts.append(f"acceptance {r['dtype']} {what} {label[new]} against {label[old]} (no slower): old "
-                            f"{o['med']:.3f} ms - new {n['med']:.3f} ms = {gain:.3f} ms vs 5-95% band {spread:.3f} ms: "
-                            f"{'MET' if gain >= -spread else 'NOT MET'}")
+            verdicts.append(f"acceptance {r['dtype']} {_object(r)} {label[new]} against {label[old]} (no slower): "
+                            f"{_verdict(r['paths'][old]['host'], r['paths'][new]['host'])}")
     d = results[0]["datagram"]
     verdicts.append(f"datagram v{d['version']}: {d['bits']} bits per field, bytes per hop by budget {d['bytes']}, "
                     f"kbit/s at chunk 300 with the header {d['kbit_per_s']}")
-    out = a.out or os.path.join(REPO, "profiles", "stream_dgram_bench")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out + ".json", "w") as f:
-        json.dump(results, f, indent=1)
-    with open(out + ".md", "w") as f:
-        f.write("\n".join(lines + [""] + verdicts) + "\n")
-    print("\n".join(lines + verdicts))
+    _write(a.out, "stream_dgram_bench", results, lines, verdicts)
+
+
+def _rtf_row(first, path, h, g):
+    return (f"| {first} | {path} | {_cell(h)} | {h['rtf']:.1f} | {_cell(g)} | {g['rtf']:.1f} |")
 
 
 def main_vocoder(a, dev):
     results = []
     for dec in a.decoder:
-        for dt in a.dtypes:
-            for B in a.batches:
-                for chunk in a.chunks:
-                    r = run_vocoder_config(dec, getattr(torch, dt), B, chunk, a.hops, a.warmup, a.rate, dev)
-                    results.append(r)
-                    print(json.dumps(r), flush=True)
+        results += _sweep(a, [(B, chunk) for B in a.batches for chunk in a.chunks], lambda dt, B, chunk:
+                          run_vocoder_config(dec, dt, B, chunk, a.hops, a.warmup, a.rate, dev))
     lines = ["| decoder | dtype | B | frames | path | host ms med (p5-p95) | RTF host | GPU ms med (p5-p95) | RTF GPU |",
              "|---|---|---|---|---|---|---|---|---|"]
     verdicts = []
     for r in results:
         for path in ("module", "eager", "replay"):
-            h, g = r["paths"][path]["rx_host"], r["paths"][path]["rx_gpu"]
-            lines.append(f"| {r['decoder']} | {r['dtype']} | {r['B']} | {r['frames']} | {path} | "
-                         f"{h['med']:.3f} ({h['p5']:.3f}-{h['p95']:.3f}) | {h['rtf']:.1f} | "
-                         f"{g['med']:.3f} ({g['p5']:.3f}-{g['p95']:.3f}) | {g['rtf']:.1f} |")
+            lines.append(_rtf_row(f"{r['decoder']} | {r['dtype']} | {r['B']} | {r['frames']}", path,
+                                  r["paths"][path]["rx_host"], r["paths"][path]["rx_gpu"]))
         if r["B"] == 1 and r["frames"] == 1:
-            m, s = r["paths"]["module"]["rx_host"], r["paths"]["replay"]["rx_host"]
-            gain = m["med"] - s["med"]
-            spread = max(m["p95"] - m["p5"], s["p95"] - s["p5"])
-            verdicts.append(f"acceptance {r['decoder']} {r['dtype']} B=1 frames=1 rx: module {m['med']:.3f} ms - replay "
-                            f"{s['med']:.3f} ms = {gain:.3f} ms vs 5-95% band {spread:.3f} ms: "
-                            f"{'MET' if gain > spread else 'NOT MET'}")
-    out = a.out or os.path.join(REPO, "profiles", "stream_bench_vocoder")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    with open(out + ".json", "w") as f:
-        json.dump(results, f, indent=1)
-    with open(out + ".md", "w") as f:
-        f.write("\n".join(lines + [""] + verdicts) + "\n")
-    print("\n".join(lines + verdicts))
+            verdicts.append(f"acceptance {r['decoder']} {r['dtype']} B=1 frames=1 rx: " +
+                            _verdict(r["paths"]["module"]["rx_host"], r["paths"]["replay"]["rx_host"], True,
+                                     ("module", "replay")))
+    _write(a.out, "stream_bench_vocoder", results, lines, verdicts)
 
 
 def main():
@@ -771,37 +648,21 @@ def main():
         if "audiodec" in a.decoder:
             sys.exit("stream_bench: --decoder audiodec cannot be combined with a vocoder")
         return main_vocoder(a, dev)
-    a.out = a.out or os.path.join(REPO, "profiles", "stream_bench")
-    results = []
-    for dt in a.dtypes:
-        for B in a.batches:
-            for chunk in a.chunks:
-                r = run_config(getattr(torch, dt), B, chunk, a.hops, a.warmup, a.rate, dev)
-                results.append(r)
-                print(json.dumps(r), flush=True)
+    results = _sweep(a, [(B, chunk) for B in a.batches for chunk in a.chunks],
+                     lambda dt, B, chunk: run_config(dt, B, chunk, a.hops, a.warmup, a.rate, dev))
     lines = ["| dtype | B | chunk | half | path | host ms med (p5-p95) | RTF host | GPU ms med (p5-p95) | RTF GPU |",
              "|---|---|---|---|---|---|---|---|---|"]
     verdicts = []
     for r in results:
         for half in ("tx", "rx"):
             for path in ("module", "eager", "replay"):
-                h, g = r["paths"][path][half + "_host"], r["paths"][path][half + "_gpu"]
-                lines.append(f"| {r['dtype']} | {r['B']} | {r['chunk']} | {half} | {path} | "
-                             f"{h['med']:.3f} ({h['p5']:.3f}-{h['p95']:.3f}) | {h['rtf']:.1f} | "
-                             f"{g['med']:.3f} ({g['p5']:.3f}-{g['p95']:.3f}) | {g['rtf']:.1f} |")
+                lines.append(_rtf_row(f"{r['dtype']} | {r['B']} | {r['chunk']} | {half}", path,
+                                      r["paths"][path][half + "_host"], r["paths"][path][half + "_gpu"]))
             if r["B"] == 1 and r["chunk"] == 300:
-                m, s = r["paths"]["module"][half + "_host"], r["paths"]["replay"][half + "_host"]
-                gain = m["med"] - s["med"]
-                spread = max(m["p95"] - m["p5"], s["p95"] - s["p5"])
-                verdicts.append(f"acceptance {r['dtype']} B=1 chunk=300 {half}: module {m['med']:.3f} ms - replay "
-                                f"{s['med']:.3f} ms = {gain:.3f} ms vs 5-95% band {spread:.3f} ms: "
-                                f"{'MET' if gain > spread else 'NOT MET'}")
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out + ".json", "w") as f:
-        json.dump(results, f, indent=1)
-    with open(a.out + ".md", "w") as f:
-        f.write("\n".join(lines + [""] + verdicts) + "\n")
-    print("\n".join(lines + verdicts))
+                verdicts.append(f"acceptance {r['dtype']} B=1 chunk=300 {half}: " +
+                                _verdict(r["paths"]["module"][half + "_host"], r["paths"]["replay"][half + "_host"],
+                                         True, ("module", "replay")))
+    _write(a.out, "stream_bench", results, lines, verdicts)
 
 
 if __name__ == "__main__":
