@@ -1,14 +1,35 @@
-"""SNR metric used as a loss term by train_denoise.py (:120, :140).
+"""Evaluation measures of the reference's mel_spectrogram.py:47-64 on the
+MI355X path, and the SNR loss term of train_denoise.py (:120, :140).
 
-The reference uses torchmetrics 1.2.0 ``SignalNoiseRatio()`` (third-party,
-absent here; parity unpinned beyond its published formula):
+The reference uses torchmetrics 1.2.0 and pystoi (third-party, absent here;
+parity unpinned beyond their published formulas, restated in fp64 by
+tests/metrics_ref.py):
+
+SignalNoiseRatio(zero_mean=False)
     snr_b = 10 * log10((sum_t target^2 + eps) / (sum_t (target - preds)^2 + eps)),
-    eps = finfo(float32).eps, zero_mean=False, mean over the batch.
-Computed by the sel_snr_fwd / sel_snr_bwd HIP kernels.
+    eps = finfo(float32).eps, mean over the batch; with zero_mean each row's
+    mean is subtracted from preds and target first.  zero_mean=False is computed
+    by the sel_snr_fwd / sel_snr_bwd HIP kernels, zero_mean=True by sel_sdr_*.
+ScaleInvariantSignalDistortionRatio(zero_mean=False)
+    alpha = (sum p t + eps) / (sum t^2 + eps), ts = alpha t,
+    10 * log10((sum ts^2 + eps) / (sum (ts - p)^2 + eps)), mean over the batch
+    (sel_sdr_fwd / sel_sdr_bwd).
+ShortTimeObjectiveIntelligibility(fs, extended=False)
+    STOI / ESTOI as DESIGN §22.1 defines them, at 10 kHz (sel_stoi); no
+    gradient.  Signals at another rate go through sel.resample.resample(x, fs,
+    10000) first; pystoi resamples with its own polyphase filter, so parity
+    with it at rates other than 10 kHz is unpinned.
+
+All of them differentiate with respect to preds only (the target is data), and
+refuse CPU tensors like the rest of the package.  The functional forms snr,
+si_sdr and stoi return the per-row values (shape preds.shape[:-1]).
 """
 import torch
 
 from . import _lib as L
+from .resample import resample
+
+STOI_FS = 10000
 
 
 class _SNRFn(torch.autograd.Function):
@@ -35,13 +56,112 @@ class _SNRFn(torch.autograd.Function):
         return gp.view(ctx.shape), None
 
 
+class _SDRFn(torch.autograd.Function):
+    """(per-row values, batch mean) of the SDR family; either output may be differentiated."""
+
+    @staticmethod
+    def forward(ctx, pred, target, scale_invariant, zero_mean):
+        L.need_device(pred, target)
+        if pred.shape != target.shape:
+            raise ValueError(f"sel.metrics: preds {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
+        T = pred.shape[-1]
+        p = pred.contiguous().float().reshape(-1, T)
+        t = target.contiguous().float().reshape(-1, T)
+        B = p.shape[0]
+        ws = L.workspace(L.lib().sel_sdr_workspace(B), p.device)
+        vals = torch.empty(B, dtype=torch.float32, device=p.device)
+        mean = torch.empty((), dtype=torch.float32, device=p.device)
+        L.call("sel_sdr_fwd", L.ptr(p), L.ptr(t), B, T, int(scale_invariant), int(zero_mean), L.ptr(vals),
+               L.ptr(mean), L.ptr(ws), ws.numel(), L.stream())
+        ctx.save_for_backward(p, t, ws)
+        ctx.shape = pred.shape
+        ctx.flags = (int(scale_invariant), int(zero_mean))
+        ctx.set_materialize_grads(False)
+        return vals.view(pred.shape[:-1]), mean
+
+    @staticmethod
+    def backward(ctx, g_vals, g_mean):
+        p, t, ws = ctx.saved_tensors
+        if g_vals is None and g_mean is None:
+            return None, None, None, None
+        B, T = p.shape
+        gv = g_vals.contiguous().float().reshape(-1) if g_vals is not None else None
+        gm = g_mean.contiguous().float() if g_mean is not None else None
+        gp = torch.empty_like(p)
+        L.call("sel_sdr_bwd", L.ptr(p), L.ptr(t), B, T, ctx.flags[0], ctx.flags[1], L.ptr(gv), L.ptr(gm), L.ptr(gp),
+               L.ptr(ws), ws.numel(), L.stream())
+        return gp.view(ctx.shape), None, None, None
+
+
+def snr(preds, target, zero_mean=False):
+    """Per-row SNR in dB (torchmetrics.functional.signal_noise_ratio)."""
+    return _SDRFn.apply(preds, target, False, bool(zero_mean))[0]
+
+
+def si_sdr(preds, target, zero_mean=False):
+    """Per-row SI-SDR in dB (torchmetrics.functional.scale_invariant_signal_distortion_ratio)."""
+    return _SDRFn.apply(preds, target, True, bool(zero_mean))[0]
+
+
+def _stoi(preds, target, fs, extended):
+    L.need_device(preds, target)
+    if preds.shape != target.shape:
+        raise ValueError(f"sel.metrics: preds {tuple(preds.shape)} and target {tuple(target.shape)} differ in shape")
+    if int(fs) != STOI_FS:
+        preds, target = resample(preds, int(fs), STOI_FS), resample(target, int(fs), STOI_FS)
+    T = preds.shape[-1]
+    p = preds.detach().contiguous().float().reshape(-1, T)
+    t = target.detach().contiguous().float().reshape(-1, T)
+    B = p.shape[0]
+    ws = L.workspace(L.lib().sel_stoi_workspace(B, T), p.device)
+    d = torch.empty(B, dtype=torch.float32, device=p.device)
+    mean = torch.empty((), dtype=torch.float32, device=p.device)
+    L.call("sel_stoi", L.ptr(t), L.ptr(p), B, T, int(bool(extended)), L.ptr(d), L.ptr(mean), None, L.ptr(ws),
+           ws.numel(), L.stream())
+    return d.view(preds.shape[:-1]), mean
+
+
+@torch.no_grad()
+def stoi(preds, target, fs, extended=False):
+    """Per-row STOI (ESTOI with extended=True); `target` is the clean signal."""
+    return _stoi(preds, target, fs, extended)[0]
+
+
 class SignalNoiseRatio(torch.nn.Module):
     """Drop-in for torchmetrics.audio.SignalNoiseRatio as called by train_denoise.py."""
 
     def __init__(self, zero_mean=False):
         super().__init__()
-        if zero_mean:
-            raise NotImplementedError("sel: only zero_mean=False (the train_denoise.py default)")
+        self.zero_mean = bool(zero_mean)
 
     def forward(self, preds, target):
+        if self.zero_mean:
+            return _SDRFn.apply(preds, target, False, True)[1]
         return _SNRFn.apply(preds, target)
+
+
+class ScaleInvariantSignalDistortionRatio(torch.nn.Module):
+    """Drop-in for torchmetrics.audio.ScaleInvariantSignalDistortionRatio (batch mean, in dB)."""
+
+    def __init__(self, zero_mean=False):
+        super().__init__()
+        self.zero_mean = bool(zero_mean)
+
+    def forward(self, preds, target):
+        return _SDRFn.apply(preds, target, True, self.zero_mean)[1]
+
+
+class ShortTimeObjectiveIntelligibility(torch.nn.Module):
+    """Drop-in for torchmetrics.audio.ShortTimeObjectiveIntelligibility (batch mean).
+    Parity with pystoi is unpinned; at fs != 10000 the resampler differs from pystoi's."""
+
+    def __init__(self, fs, extended=False):
+        super().__init__()
+        if int(fs) <= 0:
+            raise ValueError("sel.metrics: fs must be positive")
+        self.fs = int(fs)
+        self.extended = bool(extended)
+
+    @torch.no_grad()
+    def forward(self, preds, target):
+        return _stoi(preds, target, self.fs, self.extended)[1]

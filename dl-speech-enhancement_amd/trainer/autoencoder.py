@@ -107,3 +107,4 @@ class Trainer(TrainerVQGAN):
             gen_loss = gen_loss + self._adv_loss(p_, p, mode=mode)
             self._dis_loss(p_, p, mode=mode)
         self._record_loss("generator_loss", gen_loss, mode=mode)
+        self._eval_measures(y_, x)

@@ -54,3 +54,4 @@ class Trainer(TrainerVQGAN):
         gen_loss = self._vq_loss(vqloss, mode=mode)
         gen_loss = gen_loss + self._metric_loss(y_nc, x_c, mode=mode)
         self._record_loss("generator_loss", gen_loss, mode=mode)
+        self._eval_measures(y_nc, x_c)

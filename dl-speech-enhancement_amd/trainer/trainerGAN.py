@@ -139,6 +139,23 @@ class _NullBar:
         pass
 
 
+EVAL_MEASURES = ("SI-SDR", "SNR", "STOI", "ESTOI")
+
+
+def _check_eval_measures(config):
+    """config["eval_measures"] (not in the reference: absent or empty, nothing
+    changes): a list drawn from EVAL_MEASURES, recorded as eval/<name> by the
+    eval steps.  Needs config["sampling_rate"] (STOI is defined at 10 kHz)."""
+    names = config.get("eval_measures")
+    if not names:
+        return ()
+    if isinstance(names, str) or any(n not in EVAL_MEASURES for n in names):
+        raise ValueError(f"eval_measures must be a list drawn from {list(EVAL_MEASURES)}, got {names!r}")
+    if "sampling_rate" not in config:
+        raise KeyError("eval_measures needs config['sampling_rate'] (the rate of the evaluated waveforms)")
+    return tuple(dict.fromkeys(names))
+
+
 class TrainerGAN(abc.ABC):
     def __init__(self, steps, epochs, data_loader, model, criterion, optimizer, scheduler, config,
                  device=torch.device("cpu")):
@@ -156,6 +173,7 @@ class TrainerGAN(abc.ABC):
         self.total_eval_loss = LossTotals()
         self.train_max_steps = config.get("train_max_steps", 0)
         self.tqdm = _NullBar()
+        self.eval_measures = _check_eval_measures(config)
 
     @abc.abstractmethod
     def _train_step(self, batch):
@@ -261,6 +279,23 @@ class TrainerGAN(abc.ABC):
             self._record_loss("shape_loss", shape_loss, mode=mode)
             metric_loss = acc(metric_loss, shape_loss)
         return metric_loss
+
+    def _eval_measures(self, predict_y, natural_y):
+        """Record eval/<name> for each of config["eval_measures"] (batch means of
+        sel.metrics, natural_y the clean signal).  Values are local to this rank."""
+        if not self.eval_measures:
+            return
+        from sel import metrics as M
+        fs = self.config["sampling_rate"]
+        with torch.no_grad():
+            for name in self.eval_measures:
+                if name == "SI-SDR":
+                    value = M.ScaleInvariantSignalDistortionRatio()(predict_y, natural_y)
+                elif name == "SNR":
+                    value = M.SignalNoiseRatio()(predict_y, natural_y)
+                else:
+                    value = M.ShortTimeObjectiveIntelligibility(fs, extended=name == "ESTOI")(predict_y, natural_y)
+                self._record_loss(name, value, mode="eval")
 
     def _adv_loss(self, predict_p, natural_p=None, mode="train"):
         adv_loss = self.criterion["gen_adv"](predict_p)

@@ -84,3 +84,4 @@ class Trainer(TrainerGAN):
             gen_loss = gen_loss + self._adv_loss(p_, p, mode=mode)
             self._dis_loss(p_, p, mode=mode)
         self._record_loss("generator_loss", gen_loss, mode=mode)
+        self._eval_measures(y_, x)

@@ -692,6 +692,43 @@ int sel_snr_fwd(const float* pred, const float* target, int64_t B, int64_t T, do
 int sel_snr_bwd(const float* pred, const float* target, int64_t B, int64_t T, const double* sums,
                 const float* g_out, float* g_pred, sel_stream_t stream);
 
+/* ---- evaluation measures (the reference's mel_spectrogram.py:47-64) ----
+ * Every call below refuses bad arguments before any device work (null
+ * pointers, B or T <= 0, flags outside {0, 1}: SEL_ERR_ARG; a short workspace:
+ * SEL_ERR_WORKSPACE), enqueues on `stream`, allocates nothing, makes no host
+ * synchronisation and can be captured into a graph.  ws: caller-owned, 8-byte
+ * aligned, at least the matching *_workspace bytes.
+ *
+ * SDR family over the last dim of (B, T) fp32, eps = FLT_EPSILON, row sums in
+ * fp64; with zero_mean each row's mean is subtracted from both signals first.
+ *   scale_invariant = 0: 10 log10((sum t^2 + eps) / (sum (t - p)^2 + eps))
+ *   scale_invariant = 1 (torchmetrics 1.2.0 scale_invariant_signal_distortion_ratio):
+ *     alpha = (sum p t + eps) / (sum t^2 + eps), ts = alpha t,
+ *     10 log10((sum ts^2 + eps) / (sum (ts - p)^2 + eps))
+ * fwd writes vals (B) and mean (1) and leaves the row sums in ws for bwd.
+ * bwd: g_pred (B, T) = d(sum_b g_vals[b] vals[b] + g_mean[0] mean) / d pred;
+ * either of g_vals (B) / g_mean (1) may be null, not both.
+ * (scale_invariant = 0, zero_mean = 0) runs sel_snr_fwd / sel_snr_bwd: mean
+ * and (with g_vals null) g_pred are theirs bit for bit. */
+size_t sel_sdr_workspace(int64_t B);
+int sel_sdr_fwd(const float* pred, const float* target, int64_t B, int64_t T, int scale_invariant, int zero_mean,
+                float* vals /*B*/, float* mean /*1*/, void* ws, size_t ws_bytes, sel_stream_t stream);
+int sel_sdr_bwd(const float* pred, const float* target, int64_t B, int64_t T, int scale_invariant, int zero_mean,
+                const float* g_vals /*B, may be NULL*/, const float* g_mean /*1, may be NULL*/, float* g_pred,
+                const void* ws, size_t ws_bytes, sel_stream_t stream);
+/* STOI (extended = 0) / ESTOI (extended = 1) of (B, T) fp32 signals at 10 kHz,
+ * T >= 256, B <= 65535: frame 256, hop 128, Hann(258)[1:-1], frames of the
+ * clean signal more than 40 dB below its loudest dropped from both, 512-point
+ * FFT, 15 third-octave bands from 150 Hz, segments of 30 frames.
+ * d (B); mean (1, may be NULL); info (int32 3 B, may be NULL): frames, frames
+ * kept, M = kept - 1 re-framed columns, per row.  A row with M < 30 gets 1e-5.
+ * sel_stoi_band_edges: band b sums bins [edges[b], edges[b + 1]) (16 ints, host). */
+size_t sel_stoi_workspace(int64_t B, int64_t T);
+int sel_stoi(const float* clean, const float* proc, int64_t B, int64_t T, int extended, float* d /*B*/,
+             float* mean /*1, may be NULL*/, int* info /*3B, may be NULL*/, void* ws, size_t ws_bytes,
+             sel_stream_t stream);
+int sel_stoi_band_edges(int* edges /*16*/);
+
 /* ---- data pipeline: band-limited resampling ----
  * replaces torchaudio.functional.resample(x, orig, new) at dataloader/AudioDataset.py:28-33
  * (defaults: sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99; torchaudio 2.1.1
