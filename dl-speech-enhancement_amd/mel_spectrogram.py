@@ -3,8 +3,8 @@ the measures of its ``print_measures`` (:47-64).
 
 The reference builds ``mel_spectrogram = torchaudio.transforms.MelSpectrogram(48000)``
 and ``Mel_L1(pred, target) = L1(mel(pred), mel(target))``.  ``measures()``
-returns what ``print_measures`` prints, for the seven of its nine measures that
-exist here (sel.metrics); its remaining module-level code (soundfile I/O,
+returns what ``print_measures`` prints, for the eight of its nine measures that
+exist here (sel.metrics; the BSS-eval SDR on request); its remaining module-level code (soundfile I/O,
 plots, :66-118) is not part of the hot path and is not reproduced.
 
 ``MelSpectrogram`` mirrors torchaudio's transform signature and defaults
@@ -68,25 +68,32 @@ def Mel_L1(pred, target):
         return mae(mel_spectrogram(pred), mel_spectrogram(target))
 
 
-def measures(waveform1, waveform2, sample_rate=48000):
+def measures(waveform1, waveform2, sample_rate=48000, sdr=False):
     """The reference's print_measures (:47-64) as a dict of 0-d device tensors:
     every measure is called as measure(waveform1, waveform2), i.e. waveform1 is
     the prediction and waveform2 the target / clean signal.  Keys, as the
     reference names them: MAE, MSE, SNR, SI-SDR(True), SI-SDR(False), STOI,
-    Mel-L1.  Absent: SDR (torchmetrics' SignalDistortionRatio is a 512-tap
-    BSS-eval filter solve, not built here) and PESQ (the ITU-T P.862 reference
-    program, which cannot be restated).  Mel-L1 uses the module's 48 kHz mel
-    transform whatever sample_rate is, as the reference does."""
+    Mel-L1.  With sdr=True the dict also has SDR (torchmetrics'
+    SignalDistortionRatio with its defaults, a 512-tap BSS-eval filter solve:
+    sel.metrics.SignalDistortionRatio) between SNR and SI-SDR(True), where the
+    reference prints it.  Absent: PESQ (the ITU-T P.862 reference program, which
+    cannot be restated).  Mel-L1 uses the module's 48 kHz mel transform whatever
+    sample_rate is, as the reference does."""
     from sel import _lib as L
     from sel import metrics as M
     L.need_device(waveform1, waveform2)
     with torch.no_grad():
-        return {
+        out = {
             "MAE": mae(waveform1, waveform2),
             "MSE": nn.functional.mse_loss(waveform1, waveform2),
             "SNR": M.SignalNoiseRatio()(waveform1, waveform2),
+        }
+        if sdr:
+            out["SDR"] = M.SignalDistortionRatio()(waveform1, waveform2)
+        out.update({
             "SI-SDR(True)": M.ScaleInvariantSignalDistortionRatio(zero_mean=True)(waveform1, waveform2),
             "SI-SDR(False)": M.ScaleInvariantSignalDistortionRatio(zero_mean=False)(waveform1, waveform2),
             "STOI": M.ShortTimeObjectiveIntelligibility(sample_rate)(waveform1, waveform2),
             "Mel-L1": Mel_L1(waveform1, waveform2),
-        }
+        })
+        return out

@@ -95,6 +95,9 @@ SIGNATURES = {
     "sel_stoi_workspace": (SZ, [I64, I64]),
     "sel_stoi": (I32, [P, P, I64, I64, I32, P, P, P, P, SZ, P]),
     "sel_stoi_band_edges": (I32, [P]),
+    "sel_bss_sdr_chunk": (I64, []),
+    "sel_bss_sdr_workspace": (SZ, [I64, I64, I32]),
+    "sel_bss_sdr": (I32, [P, P, I64, I64, I32, I32, F64, P, P, P, P, SZ, P]),
     "sel_batchnorm_workspace": (SZ, [I64, I32]),
     "sel_batchnorm_fwd": (I32, [P, I64, I32, P, P, I32, F32, F32, P, P, P, P, P, P, SZ, P]),
     "sel_batchnorm_bwd": (I32, [P, P, I64, I32, P, P, P, I32, P, P, P, P, SZ, P]),

@@ -20,16 +20,28 @@ ShortTimeObjectiveIntelligibility(fs, extended=False)
     10000) first; pystoi resamples with its own polyphase filter, so parity
     with it at rates other than 10 kHz is unpinned.
 
+SignalDistortionRatio(use_cg_iter=None, filter_length=512, zero_mean=False, load_diag=None)
+    The BSS-eval SDR as DESIGN §23 defines it (sel_bss_sdr): fp64 linear
+    correlations of the unit-norm signals, a filter_length-tap symmetric
+    Toeplitz solve, 10 log10(coh / (1 - coh)); filter_length in [1, 512].  No
+    gradient.  A row whose prediction equals its target up to scale is +inf; a
+    silent target row is NaN (torchmetrics raises there).  At T < filter_length
+    torchmetrics' FFT reads wrapped lags; here the correlations stay linear.
+
 All of them differentiate with respect to preds only (the target is data), and
 refuse CPU tensors like the rest of the package.  The functional forms snr,
-si_sdr and stoi return the per-row values (shape preds.shape[:-1]).
+si_sdr, sdr and stoi return the per-row values (shape preds.shape[:-1]).
 """
+import math
+import warnings
+
 import torch
 
 from . import _lib as L
 from .resample import resample
 
 STOI_FS = 10000
+SDR_MAX_FILTER_LENGTH = 512
 
 
 class _SNRFn(torch.autograd.Function):
@@ -127,6 +139,48 @@ def stoi(preds, target, fs, extended=False):
     return _stoi(preds, target, fs, extended)[0]
 
 
+_warned_cg = False
+
+
+def _check_sdr_args(use_cg_iter, filter_length, load_diag):
+    global _warned_cg
+    if isinstance(filter_length, bool) or int(filter_length) != filter_length or \
+            not 1 <= int(filter_length) <= SDR_MAX_FILTER_LENGTH:
+        raise ValueError(f"sel.metrics: filter_length must be an integer in [1, {SDR_MAX_FILTER_LENGTH}], "
+                         f"got {filter_length!r}")
+    if load_diag is not None and not (math.isfinite(float(load_diag)) and float(load_diag) >= 0.0):
+        raise ValueError(f"sel.metrics: load_diag must be finite and not negative, got {load_diag!r}")
+    if use_cg_iter is not None and not _warned_cg:
+        _warned_cg = True
+        warnings.warn("sel.metrics: use_cg_iter needs fast-bss-eval's conjugate-gradient solve, which is not built; "
+                      "the direct solve is used", UserWarning, stacklevel=3)
+    return int(filter_length), 0.0 if load_diag is None else float(load_diag)
+
+
+def _bss_sdr(preds, target, filter_length, zero_mean, load_diag):
+    L.need_device(preds, target)
+    if preds.shape != target.shape:
+        raise ValueError(f"sel.metrics: preds {tuple(preds.shape)} and target {tuple(target.shape)} differ in shape")
+    T = preds.shape[-1]
+    p = preds.detach().contiguous().float().reshape(-1, T)
+    t = target.detach().contiguous().float().reshape(-1, T)
+    B = p.shape[0]
+    ws = L.workspace(L.lib().sel_bss_sdr_workspace(B, T, filter_length), p.device)
+    vals = torch.empty(B, dtype=torch.float32, device=p.device)
+    mean = torch.empty((), dtype=torch.float32, device=p.device)
+    L.call("sel_bss_sdr", L.ptr(p), L.ptr(t), B, T, filter_length, int(bool(zero_mean)), load_diag, L.ptr(vals),
+           L.ptr(mean), None, L.ptr(ws), ws.numel(), L.stream())
+    return vals.view(preds.shape[:-1]), mean
+
+
+@torch.no_grad()
+def sdr(preds, target, use_cg_iter=None, filter_length=512, zero_mean=False, load_diag=None):
+    """Per-row BSS-eval SDR in dB (torchmetrics.functional.signal_distortion_ratio,
+    direct solve).  No autograd: the result carries no grad_fn."""
+    filter_length, load_diag = _check_sdr_args(use_cg_iter, filter_length, load_diag)
+    return _bss_sdr(preds, target, filter_length, zero_mean, load_diag)[0]
+
+
 class SignalNoiseRatio(torch.nn.Module):
     """Drop-in for torchmetrics.audio.SignalNoiseRatio as called by train_denoise.py."""
 
@@ -149,6 +203,20 @@ class ScaleInvariantSignalDistortionRatio(torch.nn.Module):
 
     def forward(self, preds, target):
         return _SDRFn.apply(preds, target, True, self.zero_mean)[1]
+
+
+class SignalDistortionRatio(torch.nn.Module):
+    """Drop-in for torchmetrics.audio.SignalDistortionRatio (batch mean, in dB);
+    filter_length in [1, 512].  No autograd: the result carries no grad_fn."""
+
+    def __init__(self, use_cg_iter=None, filter_length=512, zero_mean=False, load_diag=None):
+        super().__init__()
+        self.filter_length, self.load_diag = _check_sdr_args(use_cg_iter, filter_length, load_diag)
+        self.zero_mean = bool(zero_mean)
+
+    @torch.no_grad()
+    def forward(self, preds, target):
+        return _bss_sdr(preds, target, self.filter_length, self.zero_mean, self.load_diag)[1]
 
 
 class ShortTimeObjectiveIntelligibility(torch.nn.Module):

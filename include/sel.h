@@ -728,6 +728,25 @@ int sel_stoi(const float* clean, const float* proc, int64_t B, int64_t T, int ex
              float* mean /*1, may be NULL*/, int* info /*3B, may be NULL*/, void* ws, size_t ws_bytes,
              sel_stream_t stream);
 int sel_stoi_band_edges(int* edges /*16*/);
+/* BSS-eval SDR: torchmetrics 1.2.0 signal_distortion_ratio with the
+ * direct solve, over the last dim of (B, T) fp32, L = filter_length in [1, 512],
+ * B <= 65535, T <= 2^32.  In fp64: subtract each row's mean (zero_mean),
+ * t /= max(||t||, 1e-6), p /= max(||p||, 1e-6), r[k] = sum_n t[n] t[n + k] and
+ * b[k] = sum_n t[n] p[n + k] for k < L (LINEAR correlations: terms with
+ * n + k >= T are absent, lags k >= T are 0; torchmetrics' wrapped lags at T < L
+ * are not reproduced), r[0] += load_diag (0: none; negative or not finite:
+ * SEL_ERR_ARG), sol = toeplitz(r)^-1 b (Levinson recursion), coh = b . sol,
+ * vals[row] = 10 log10(coh / (1 - coh)).  1 - coh <= 0 gives +inf; a silent
+ * target (r[0] <= 0) gives NaN in that row and in mean, other rows unaffected.
+ * vals (B); mean (1, may be NULL): the batch mean; corr (B, 2, L) fp64, may be
+ * NULL: r then b as the solve sees them.  No atomics: the same bits run to run.
+ * sel_bss_sdr_chunk: samples of n per correlation block (host). */
+int64_t sel_bss_sdr_chunk(void);
+size_t sel_bss_sdr_workspace(int64_t B, int64_t T, int filter_length);
+int sel_bss_sdr(const float* pred, const float* target, int64_t B, int64_t T, int filter_length, int zero_mean,
+                double load_diag, float* vals /*B*/, float* mean /*1, may be NULL*/,
+                double* corr /*(B, 2, filter_length), may be NULL*/, void* ws, size_t ws_bytes,
+                sel_stream_t stream);
 
 /* ---- data pipeline: band-limited resampling ----
  * replaces torchaudio.functional.resample(x, orig, new) at dataloader/AudioDataset.py:28-33
