@@ -459,6 +459,311 @@ __global__ __launch_bounds__(256) void k_stoi_finish(const double* __restrict__ 
   if (threadIdx.x == 0 && mean) mean[0] = float(acc / double(B));
 }
 
+// ---------------------------------------------------------------------------
+// Gradient of STOI / ESTOI with respect to the processed signal.
+// Three gathers, each summed in a fixed order (no atomics): the segments'
+// adjoints, the columns' (two transforms each), the samples'.
+// ---------------------------------------------------------------------------
+
+// g_row / (n J): the factor of one segment's sum in the incoming gradient
+__device__ __forceinline__ double stoi_seg_weight(const float* __restrict__ g_d, const float* __restrict__ g_mean,
+                                                  int64_t b, int64_t B, int M, int extended) {
+  double g = 0.0;
+  if (g_d) g += double(g_d[b]);
+  if (g_mean) g += double(g_mean[0]) / double(B);
+  return g / (double(extended ? kSeg : kBands) * double(M - kSeg + 1));
+}
+
+// One block per segment s < J: the gradient of the segment's sum with respect
+// to its 30 x 15 processed band magnitudes, times g_row / (n J), to
+// gseg (B, F - 30, 30, 15) fp64.  The forward of k_stoi_seg is recomputed.
+__global__ __launch_bounds__(64) void k_stoi_seg_bwd(const double* __restrict__ bands, const int* __restrict__ cnt,
+                                                     int64_t B, int F, int extended, const float* __restrict__ g_d,
+                                                     const float* __restrict__ g_mean, double* __restrict__ gseg) {
+  __shared__ double X[kSeg * kBands], Y[kSeg * kBands];
+  __shared__ double nrm[kBands];
+  const int lane = threadIdx.x;
+  const int s = blockIdx.x;
+  const int64_t b = blockIdx.y;
+  const int M = cnt[3 * b + 2];
+  if (M < kSeg || s > M - kSeg) return;  // block-uniform
+  const double* __restrict__ bx = bands + ((b * 2) * int64_t(F - 1) + s) * kBands;
+  const double* __restrict__ by = bands + ((b * 2 + 1) * int64_t(F - 1) + s) * kBands;
+  double* __restrict__ go = gseg + (b * int64_t(F - kSeg) + s) * (kSeg * kBands);
+  for (int i = lane; i < kSeg * kBands; i += 64) {  // [column][band], as stored
+    X[i] = bx[i];
+    Y[i] = by[i];
+  }
+  __syncthreads();
+  const double wgt = stoi_seg_weight(g_d, g_mean, b, B, M, extended);
+  if (!extended) {
+    if (lane < kBands) {
+      double nx = 0.0, ny = 0.0;
+      for (int c = 0; c < kSeg; ++c) {
+        const double x = X[c * kBands + lane], y = Y[c * kBands + lane];
+        nx += x * x;
+        ny += y * y;
+      }
+      const double rx = sqrt(nx), ry = sqrt(ny);
+      const double scale = rx / (ry + kEps);
+      const double beta = 1.0 + 5.623413251903491;  // 1 + 10^(15 / 20)
+      double sx = 0.0, sy = 0.0;
+      for (int c = 0; c < kSeg; ++c) {
+        const double x = X[c * kBands + lane];
+        sx += x;
+        sy += fmin(scale * Y[c * kBands + lane], x * beta);
+      }
+      const double mx = sx / kSeg, my = sy / kSeg;
+      double sxx = 0.0, syy = 0.0, sxy = 0.0;
+      for (int c = 0; c < kSeg; ++c) {
+        const double x = X[c * kBands + lane];
+        const double dx = x - mx, dy = fmin(scale * Y[c * kBands + lane], x * beta) - my;
+        sxx += dx * dx;
+        syy += dy * dy;
+        sxy += dx * dy;
+      }
+      // rho = sxy / (a q): d rho / d dy = ca dx - cb dy, then the mean removal's adjoint
+      const double rs = sqrt(syy), a = sqrt(sxx) + kEps, q = rs + kEps;
+      const double ca = 1.0 / (a * q), cb = rs > 0.0 ? sxy / (a * q * q * rs) : 0.0;
+      double hm = 0.0;
+      for (int c = 0; c < kSeg; ++c) {
+        const double x = X[c * kBands + lane];
+        hm += ca * (x - mx) - cb * (fmin(scale * Y[c * kBands + lane], x * beta) - my);
+      }
+      hm /= kSeg;
+      // y' = scale y where scale y < beta x (scale depends on every y of the band), a constant elsewhere
+      double dot = 0.0;
+      for (int c = 0; c < kSeg; ++c) {
+        const double x = X[c * kBands + lane], y = Y[c * kBands + lane];
+        if (scale * y < x * beta) dot += (ca * (x - mx) - cb * (scale * y - my) - hm) * y;
+      }
+      const double dscale = ry > 0.0 ? -rx / ((ry + kEps) * (ry + kEps) * ry) : 0.0;
+      for (int c = 0; c < kSeg; ++c) {
+        const double x = X[c * kBands + lane], y = Y[c * kBands + lane];
+        double g = dot * dscale * y;
+        if (scale * y < x * beta) g += scale * (ca * (x - mx) - cb * (scale * y - my) - hm);
+        go[c * kBands + lane] = wgt * g;
+      }
+    }
+    return;
+  }
+  if (lane < kBands) {  // rows: each band over the 30 columns; Y keeps the row-normalised values
+    for (int sgn = 0; sgn < 2; ++sgn) {
+      double* A = sgn ? Y : X;
+      double m = 0.0;
+      for (int c = 0; c < kSeg; ++c) m += A[c * kBands + lane];
+      m /= kSeg;
+      double n2 = 0.0;
+      for (int c = 0; c < kSeg; ++c) {
+        const double dv = A[c * kBands + lane] - m;
+        n2 += dv * dv;
+      }
+      const double r = sqrt(n2);
+      if (sgn) nrm[lane] = r;
+      const double inv = 1.0 / (r + kEps);
+      for (int c = 0; c < kSeg; ++c) A[c * kBands + lane] = (A[c * kBands + lane] - m) * inv;
+    }
+  }
+  __syncthreads();
+  if (lane < kSeg) {  // columns: d rho_c / d (row-normalised y), over X's column (no longer needed)
+    double mx = 0.0, my = 0.0;
+    for (int k = 0; k < kBands; ++k) {
+      mx += X[lane * kBands + k];
+      my += Y[lane * kBands + k];
+    }
+    mx /= kBands;
+    my /= kBands;
+    double sxx = 0.0, syy = 0.0, sxy = 0.0;
+    for (int k = 0; k < kBands; ++k) {
+      const double dx = X[lane * kBands + k] - mx, dy = Y[lane * kBands + k] - my;
+      sxx += dx * dx;
+      syy += dy * dy;
+      sxy += dx * dy;
+    }
+    const double rs = sqrt(syy), a = sqrt(sxx) + kEps, q = rs + kEps;
+    const double ca = 1.0 / (a * q), cb = rs > 0.0 ? sxy / (a * q * q * rs) : 0.0;
+    double hm = 0.0;
+    for (int k = 0; k < kBands; ++k) {
+      const double h = ca * (X[lane * kBands + k] - mx) - cb * (Y[lane * kBands + k] - my);
+      X[lane * kBands + k] = h;
+      hm += h;
+    }
+    hm /= kBands;
+    for (int k = 0; k < kBands; ++k) X[lane * kBands + k] -= hm;
+  }
+  __syncthreads();
+  if (lane < kBands) {  // rows: through r = v / (||v|| + EPS), v = y - mean y
+    const double r = nrm[lane], q = r + kEps;
+    double dot = 0.0;
+    for (int c = 0; c < kSeg; ++c) dot += X[c * kBands + lane] * Y[c * kBands + lane];
+    const double cr = r > 0.0 ? dot / r : 0.0;
+    double gm = 0.0;
+    for (int c = 0; c < kSeg; ++c) gm += X[c * kBands + lane] / q - cr * Y[c * kBands + lane];
+    gm /= kSeg;
+    for (int c = 0; c < kSeg; ++c)
+      go[c * kBands + lane] = wgt * (X[c * kBands + lane] / q - cr * Y[c * kBands + lane] - gm);
+  }
+}
+
+// 512-point forward transform of v (lane holds points lane + 64 r) into buf in
+// natural order: the three Stockham radix-8 passes of k_stoi_bands, which keeps
+// its own copy so that its code, and with it the forward's bits, stay as they were.
+__device__ __forceinline__ void fft512(cf (&v)[8], cf* __restrict__ buf, const cf* __restrict__ tw, int lane) {
+  dft8(v);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) buf[lane * 8 + q] = v[q];
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 8; ++r) v[r] = buf[lane + 64 * r];
+  __syncthreads();
+  {
+    const int k = lane & 7;
+#pragma unroll
+    for (int r = 1; r < 8; ++r) v[r] = cmul(v[r], tw[k * r * 8]);
+    dft8(v);
+    const int base = (lane >> 3) * 64 + k;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) buf[base + q * 8] = v[q];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int r = 0; r < 8; ++r) v[r] = buf[lane + 64 * r];
+  __syncthreads();
+#pragma unroll
+  for (int r = 1; r < 8; ++r) v[r] = cmul(v[r], tw[lane * r]);
+  dft8(v);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) buf[lane + q * 64] = v[q];
+  __syncthreads();
+}
+
+// One wave per re-framed column j < M of a row with M >= 30.  g_band[j] is the
+// sum over the at most 30 segments holding column j, in ascending s.  The
+// column's spectrum Y is recomputed as k_stoi_bands does (processed signal
+// only); with G_k = (g_band / band) Y_k on bins 7..218 (0 where band is 0) the
+// gradient with respect to the column of the overlap-added signal is
+// gz[n] = w[n] Re sum_k G_k e^{+2 pi i k n / 512}, n < 256: w[n] times the real
+// part of the forward transform of conj(G).  gz: (B, F - 1, 256) fp64.
+__global__ __launch_bounds__(64) void k_stoi_col_bwd(const float* __restrict__ proc, int64_t T, int F,
+                                                     const int* __restrict__ kidx, const int* __restrict__ cnt,
+                                                     const double* __restrict__ bands,
+                                                     const double* __restrict__ gseg, double* __restrict__ gz) {
+  __shared__ double w[kFrame];
+  __shared__ cf tw[kNfft];
+  __shared__ cf buf[kNfft];
+  __shared__ double coef[kBands];
+  const int lane = threadIdx.x;
+  const int j = blockIdx.x;
+  const int64_t b = blockIdx.y;
+  const int M = cnt[3 * b + 2];
+  if (M < kSeg || j >= M) return;  // block-uniform
+#pragma unroll
+  for (int r = 0; r < 4; ++r) w[lane + 64 * r] = stoi_window(lane + 64 * r);
+#pragma unroll
+  for (int r = 0; r < 8; ++r) {
+    double sn, cs;
+    sincospi(-2.0 * double(lane + 64 * r) / double(kNfft), &sn, &cs);
+    tw[lane + 64 * r] = cf{cs, sn};
+  }
+  if (lane < kBands) {
+    const int J = M - kSeg + 1;
+    const int s0 = j - (kSeg - 1) > 0 ? j - (kSeg - 1) : 0, s1 = j < J - 1 ? j : J - 1;
+    const double* __restrict__ gs = gseg + b * int64_t(F - kSeg) * (kSeg * kBands);
+    double g = 0.0;
+    for (int s = s0; s <= s1; ++s) g += gs[(int64_t(s) * kSeg + (j - s)) * kBands + lane];
+    const double bd = bands[((b * 2 + 1) * int64_t(F - 1) + j) * kBands + lane];
+    coef[lane] = bd != 0.0 ? g / bd : 0.0;
+  }
+  __syncthreads();
+  const int* __restrict__ kr = kidx + b * F;
+  const int k0 = kr[j], kp = kr[j + 1], km = j > 0 ? kr[j - 1] : -1;
+  const float* __restrict__ xp = proc + b * T;
+  cf v[8];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int n = lane + 64 * r;
+    double ap = w[n] * double(xp[int64_t(k0) * kHop + n]);
+    if (r < 2) {
+      if (km >= 0) ap += w[n + kHop] * double(xp[int64_t(km) * kHop + kHop + n]);
+    } else {
+      ap += w[n - kHop] * double(xp[int64_t(kp) * kHop + n - kHop]);
+    }
+    v[r] = cf{w[n] * ap, 0.0};
+  }
+#pragma unroll
+  for (int r = 4; r < 8; ++r) v[r] = cf{0.0, 0.0};
+  fft512(v, buf, tw, lane);
+  // conj(G_k) on the bins of the bands, zero elsewhere (bins >= 256 hold none)
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int k = lane + 64 * r;
+    v[r] = cf{0.0, 0.0};
+    if (k >= band_edge(0) && k < band_edge(kBands)) {
+      int bd = 0;
+      while (k >= band_edge(bd + 1)) ++bd;
+      const double c = coef[bd];
+      v[r] = cf{c * buf[k].x, -c * buf[k].y};
+    }
+  }
+#pragma unroll
+  for (int r = 4; r < 8; ++r) v[r] = cf{0.0, 0.0};
+  __syncthreads();
+  fft512(v, buf, tw, lane);
+  double* __restrict__ out = gz + (b * int64_t(F - 1) + j) * kFrame;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) out[lane + 64 * r] = w[lane + 64 * r] * buf[lane + 64 * r].x;
+}
+
+// inv[i] = position of frame i in the row's kept list, or -1: a binary search per frame
+__global__ __launch_bounds__(256) void k_stoi_inv(const int* __restrict__ kidx, const int* __restrict__ cnt, int F,
+                                                  int* __restrict__ inv) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int64_t b = blockIdx.y;
+  if (i >= F) return;
+  const int* __restrict__ kr = kidx + b * F;
+  int lo = 0, hi = cnt[3 * b + 1];  // first position with kr[pos] >= i
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (kr[mid] < i) lo = mid + 1; else hi = mid;
+  }
+  inv[b * F + i] = lo < cnt[3 * b + 1] && kr[lo] == i ? lo : -1;
+}
+
+// One thread per sample t.  Frames t / 128 - 1 and t / 128 cover it; a kept
+// frame at position q adds w[n] times its sample of column q and of column
+// q + 1 (n >= 128) or q - 1 (n < 128): at most four terms, frames then columns
+// ascending.  0 for a row with M < 30, for samples no kept frame covers and for
+// the tail past the last frame.
+__global__ __launch_bounds__(256) void k_stoi_gather(const double* __restrict__ gz, const int* __restrict__ inv,
+                                                     const int* __restrict__ cnt, int64_t T, int F,
+                                                     float* __restrict__ g_proc) {
+  __shared__ double w[kFrame];
+  w[threadIdx.x] = stoi_window(threadIdx.x);
+  __syncthreads();
+  const int64_t t = int64_t(blockIdx.x) * 256 + threadIdx.x;
+  const int64_t b = blockIdx.y;
+  if (t >= T) return;
+  const int M = cnt[3 * b + 2];
+  double acc = 0.0;
+  if (M >= kSeg) {
+    const double* __restrict__ gr = gz + b * int64_t(F - 1) * kFrame;
+    const int i1 = int(t / kHop);
+    for (int i = i1 - 1; i <= i1; ++i) {
+      if (i < 0 || i >= F) continue;
+      const int q = inv[b * F + i];
+      if (q < 0) continue;
+      const int n = int(t - int64_t(i) * kHop);  // i1 - 1: [128, 256); i1: [0, 128)
+      const int ja = n < kHop ? q - 1 : q, jb = ja + 1;
+      const int na = n < kHop ? n + kHop : n, nb = n < kHop ? n : n - kHop;
+      double c = 0.0;
+      if (ja >= 0 && ja < M) c += gr[int64_t(ja) * kFrame + na];
+      if (jb < M) c += gr[int64_t(jb) * kFrame + nb];
+      acc += w[n] * c;
+    }
+  }
+  g_proc[b * T + t] = float(acc);
+}
+
 }  // namespace metrics
 }  // namespace sel
 
@@ -558,6 +863,56 @@ int sel_stoi(const float* clean, const float* proc, int64_t B, int64_t T, int ex
     SEL_LAUNCH_CHECK();
   }
   hipLaunchKernelGGL(k_stoi_finish, dim3(1), dim3(256), 0, s, seg, cnt, B, F, extended, d, mean);
+  SEL_LAUNCH_CHECK();
+  return SEL_OK;
+}
+
+// fp64 first: the segments' adjoints ((F - 30) x 30 x 15 per row) and the columns'
+// ((F - 1) x 256); then the inverse kept-frame index (F ints), rounded up to 8 bytes
+size_t sel_stoi_bwd_workspace(int64_t B, int64_t T) {
+  if (B <= 0 || T < kFrame) return 0;
+  const size_t F = size_t(stoi_frames(T));
+  const size_t J = F > size_t(kSeg) ? F - kSeg : 0;
+  const size_t bytes = size_t(B) * ((J * kSeg * kBands + (F - 1) * kFrame) * sizeof(double) + F * sizeof(int));
+  return (bytes + 7) / 8 * 8;
+}
+
+int sel_stoi_bwd(const float* clean, const float* proc, int64_t B, int64_t T, int extended, const float* g_d,
+                 const float* g_mean, float* g_proc, const void* ws_fwd, size_t ws_fwd_bytes, void* ws_bwd,
+                 size_t ws_bwd_bytes, sel_stream_t stream) {
+  SEL_REQUIRE(clean && proc && g_proc && ws_fwd && ws_bwd, SEL_ERR_ARG, "sel_stoi_bwd: null pointer");
+  SEL_REQUIRE(g_d || g_mean, SEL_ERR_ARG, "sel_stoi_bwd: no incoming gradient");
+  SEL_REQUIRE(B > 0 && B <= 65535, SEL_ERR_ARG, "sel_stoi_bwd: B must be in [1, 65535]");
+  SEL_REQUIRE(T >= kFrame && T <= (int64_t(1) << 30), SEL_ERR_ARG, "sel_stoi_bwd: T must be in [256, 2^30]");
+  SEL_REQUIRE((extended | 1) == 1, SEL_ERR_ARG, "sel_stoi_bwd: extended must be 0 or 1");
+  SEL_REQUIRE(reinterpret_cast<uintptr_t>(ws_fwd) % 8 == 0 && reinterpret_cast<uintptr_t>(ws_bwd) % 8 == 0,
+              SEL_ERR_ARG, "sel_stoi_bwd: workspace not 8-byte aligned");
+  SEL_REQUIRE(ws_fwd_bytes >= sel_stoi_workspace(B, T), SEL_ERR_WORKSPACE,
+              "sel_stoi_bwd: forward workspace too small");
+  SEL_REQUIRE(ws_bwd_bytes >= sel_stoi_bwd_workspace(B, T), SEL_ERR_WORKSPACE,
+              "sel_stoi_bwd: backward workspace too small");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const int F = int(stoi_frames(T));
+  const int J = F > kSeg ? F - kSeg : 0;
+  // the forward's layout (sel_stoi)
+  const double* bands = static_cast<const double*>(ws_fwd) + size_t(B) * J;
+  const int* kidx = reinterpret_cast<const int*>(bands + size_t(B) * 2 * (F - 1) * kBands) + size_t(B) * F;
+  const int* cnt = kidx + size_t(B) * F;
+  double* gseg = static_cast<double*>(ws_bwd);
+  double* gz = gseg + size_t(B) * J * kSeg * kBands;
+  int* inv = reinterpret_cast<int*>(gz + size_t(B) * (F - 1) * kFrame);
+  if (J > 0) {  // fewer than 31 frames: every row is the constant 1e-5 and the gather writes zeros
+    hipLaunchKernelGGL(k_stoi_seg_bwd, dim3(unsigned(J), unsigned(B)), dim3(64), 0, s, bands, cnt, B, F, extended,
+                       g_d, g_mean, gseg);
+    SEL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_stoi_col_bwd, dim3(unsigned(F - 1), unsigned(B)), dim3(64), 0, s, proc, T, F, kidx, cnt,
+                       bands, gseg, gz);
+    SEL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_stoi_inv, dim3(unsigned((F + 255) / 256), unsigned(B)), dim3(256), 0, s, kidx, cnt, F, inv);
+    SEL_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(k_stoi_gather, dim3(unsigned((T + 255) / 256), unsigned(B)), dim3(256), 0, s, gz, inv, cnt, T, F,
+                     g_proc);
   SEL_LAUNCH_CHECK();
   return SEL_OK;
 }

@@ -75,6 +75,39 @@ __global__ __launch_bounds__(256) void k_resample(const float* __restrict__ x, i
   y[wav * out_len + j] = acc;
 }
 
+// The transpose, as a gather: one thread per input sample s sums gy[f n + p] *
+// K[p][s - f o + w] over the output frames f whose window [f o - w, f o + w + o)
+// contains s and their phases p, in ascending (f, p); no atomics.
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_resample_bwd(const float* __restrict__ gy, int64_t len, Plan p,
+                                                      const float* __restrict__ table, int64_t out_len,
+                                                      float* __restrict__ gx) {
+  extern __shared__ float taps_lds[];
+  const float* taps = table;
+  if constexpr (LDS) {
+    const int tsize = p.n * p.taps;
+    for (int i = threadIdx.x; i < tsize; i += blockDim.x) taps_lds[i] = table[i];
+    __syncthreads();
+    taps = taps_lds;
+  }
+  const int64_t wav = blockIdx.y;
+  const int64_t s = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (s >= len) return;
+  const float* g = gy + wav * out_len;
+  // s - f o + w in [0, taps)  <=>  floor((s - w) / o) <= f <= floor((s + w) / o)
+  const int64_t f0 = s >= p.w ? (s - p.w) / p.o : 0;
+  const int64_t f1 = (s + p.w) / p.o;
+  float acc = 0.f;
+  for (int64_t f = f0; f <= f1; ++f) {
+    const int i = int(s - f * p.o + p.w);
+    for (int ph = 0; ph < p.n; ++ph) {
+      const int64_t j = f * p.n + ph;
+      if (j < out_len) acc = fmaf(g[j], taps[ph * p.taps + i], acc);
+    }
+  }
+  gx[wav * len + s] = acc;
+}
+
 }  // namespace resample
 }  // namespace sel
 
@@ -140,6 +173,29 @@ int sel_resample(const float* x, int64_t n_wavs, int64_t len, int orig_freq, int
                        out_len, y);
   else
     hipLaunchKernelGGL(k_resample<false>, grid, dim3(256), 0, s, x, len, p, table, out_len, y);
+  SEL_LAUNCH_CHECK();
+  return SEL_OK;
+}
+
+/* sel_resample's refusals; the argument checks come first, so they can be seen without a device */
+int sel_resample_bwd(const float* gy, int64_t n_wavs, int64_t len, int orig_freq, int new_freq,
+                     int lowpass_filter_width, float rolloff, const float* table, float* gx, sel_stream_t stream) {
+  int nph, ntaps;
+  if (int rc = sel_resample_plan(orig_freq, new_freq, lowpass_filter_width, rolloff, &nph, &ntaps)) return rc;
+  SEL_REQUIRE(n_wavs >= 0 && len > 0, SEL_ERR_ARG, "bad waveform shape (%lld, %lld)", (long long)n_wavs,
+              (long long)len);
+  SEL_REQUIRE(n_wavs <= 65535, SEL_ERR_UNSUPPORTED, "at most 65535 waveforms per call");
+  SEL_REQUIRE(initialized(), SEL_ERR_STATE, "sel_init() has not succeeded");
+  const Plan p = plan(orig_freq, new_freq, lowpass_filter_width, rolloff);
+  const int64_t out_len = sel_resample_out_len(len, orig_freq, new_freq);
+  if (n_wavs == 0) return SEL_OK;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  dim3 grid(unsigned((len + 255) / 256), unsigned(n_wavs));
+  if (p.n * p.taps <= kLdsTable)
+    hipLaunchKernelGGL(k_resample_bwd<true>, grid, dim3(256), size_t(p.n) * p.taps * sizeof(float), s, gy, len, p,
+                       table, out_len, gx);
+  else
+    hipLaunchKernelGGL(k_resample_bwd<false>, grid, dim3(256), 0, s, gy, len, p, table, out_len, gx);
   SEL_LAUNCH_CHECK();
   return SEL_OK;
 }

@@ -95,6 +95,8 @@ SIGNATURES = {
     "sel_stoi_workspace": (SZ, [I64, I64]),
     "sel_stoi": (I32, [P, P, I64, I64, I32, P, P, P, P, SZ, P]),
     "sel_stoi_band_edges": (I32, [P]),
+    "sel_stoi_bwd_workspace": (SZ, [I64, I64]),
+    "sel_stoi_bwd": (I32, [P, P, I64, I64, I32, P, P, P, P, SZ, P, SZ, P]),
     "sel_bss_sdr_chunk": (I64, []),
     "sel_bss_sdr_workspace": (SZ, [I64, I64, I32]),
     "sel_bss_sdr": (I32, [P, P, I64, I64, I32, I32, F64, P, P, P, P, SZ, P]),
@@ -105,6 +107,7 @@ SIGNATURES = {
     "sel_resample_out_len": (I64, [I64, I32, I32]),
     "sel_resample_kernel": (I32, [I32, I32, I32, F32, P]),
     "sel_resample": (I32, [P, I64, I64, I32, I32, I32, F32, P, P, P]),
+    "sel_resample_bwd": (I32, [P, I64, I64, I32, I32, I32, F32, P, P, P]),
     "sel_shape_loss_workspace": (SZ, [I64, I64, I32]),
     "sel_shape_loss_fwd": (I32, [P, P, I64, I64, I32, P, P, P, P, SZ, P]),
     "sel_shape_loss_bwd": (I32, [P, I64, I64, I32, P, P, P, F32, P, P]),

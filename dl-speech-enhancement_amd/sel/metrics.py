@@ -16,8 +16,9 @@ ScaleInvariantSignalDistortionRatio(zero_mean=False)
     (sel_sdr_fwd / sel_sdr_bwd).
 ShortTimeObjectiveIntelligibility(fs, extended=False)
     STOI / ESTOI as DESIGN §22.1 defines them, at 10 kHz (sel_stoi); no
-    gradient.  Signals at another rate go through sel.resample.resample(x, fs,
-    10000) first; pystoi resamples with its own polyphase filter, so parity
+    gradient (stoi_loss_values and losses.STOILoss carry one, through
+    sel_stoi_bwd and sel_resample_bwd: DESIGN §24).  Signals at another rate
+    go through sel.resample.resample(x, fs, 10000) first; pystoi resamples with its own polyphase filter, so parity
     with it at rates other than 10 kHz is unpinned.
 
 SignalDistortionRatio(use_cg_iter=None, filter_length=512, zero_mean=False, load_diag=None)
@@ -137,6 +138,63 @@ def _stoi(preds, target, fs, extended):
 def stoi(preds, target, fs, extended=False):
     """Per-row STOI (ESTOI with extended=True); `target` is the clean signal."""
     return _stoi(preds, target, fs, extended)[0]
+
+
+class _STOIFn(torch.autograd.Function):
+    """(per-row d, batch mean) of STOI / ESTOI at 10 kHz with the gradient with
+    respect to preds; either output may be differentiated.  The
+    silent-frame mask is a constant selection and target is data."""
+
+    @staticmethod
+    def forward(ctx, preds, target, extended):
+        L.need_device(preds, target)
+        if preds.shape != target.shape:
+            raise ValueError(f"sel.metrics: preds {tuple(preds.shape)} and target {tuple(target.shape)} differ in shape")
+        T = preds.shape[-1]
+        p = preds.contiguous().float().reshape(-1, T)
+        t = target.contiguous().float().reshape(-1, T)
+        B = p.shape[0]
+        ws = L.workspace(L.lib().sel_stoi_workspace(B, T), p.device)
+        d = torch.empty(B, dtype=torch.float32, device=p.device)
+        mean = torch.empty((), dtype=torch.float32, device=p.device)
+        L.call("sel_stoi", L.ptr(t), L.ptr(p), B, T, int(bool(extended)), L.ptr(d), L.ptr(mean), None, L.ptr(ws),
+               ws.numel(), L.stream())
+        ctx.save_for_backward(p, t, ws)
+        ctx.shape = preds.shape
+        ctx.extended = int(bool(extended))
+        ctx.set_materialize_grads(False)
+        return d.view(preds.shape[:-1]), mean
+
+    @staticmethod
+    def backward(ctx, g_d, g_mean):
+        p, t, ws = ctx.saved_tensors
+        if g_d is None and g_mean is None:
+            return None, None, None
+        B, T = p.shape
+        gd = g_d.contiguous().float().reshape(-1) if g_d is not None else None
+        gm = g_mean.contiguous().float() if g_mean is not None else None
+        wsb = L.workspace(L.lib().sel_stoi_bwd_workspace(B, T), p.device)
+        gp = torch.empty_like(p)
+        L.call("sel_stoi_bwd", L.ptr(t), L.ptr(p), B, T, ctx.extended, L.ptr(gd), L.ptr(gm), L.ptr(gp), L.ptr(ws),
+               ws.numel(), L.ptr(wsb), wsb.numel(), L.stream())
+        return gp.view(ctx.shape), None, None
+
+
+def _stoi_grad(preds, target, fs, extended):
+    L.need_device(preds, target)
+    if preds.shape != target.shape:
+        raise ValueError(f"sel.metrics: preds {tuple(preds.shape)} and target {tuple(target.shape)} differ in shape")
+    if int(fs) != STOI_FS:
+        preds = resample(preds, int(fs), STOI_FS, differentiable=True)
+        target = resample(target.detach(), int(fs), STOI_FS)
+    return _STOIFn.apply(preds, target.detach(), bool(extended))
+
+
+def stoi_loss_values(preds, target, fs, extended=False):
+    """Per-row STOI (ESTOI with extended=True) that carries the gradient to preds;
+    `target` is the clean signal.  At fs != 10000 preds goes through the
+    differentiable resampler first (sel_resample / sel_resample_bwd)."""
+    return _stoi_grad(preds, target, fs, extended)[0]
 
 
 _warned_cg = False

@@ -25,10 +25,47 @@ def _table_host(orig_freq, new_freq, lowpass_filter_width, rolloff):
 _DEV_TABLES = {}
 
 
+def _table_dev(o, n, lowpass_filter_width, rolloff, device):
+    key = (o, n, lowpass_filter_width, rolloff, device)
+    tab = _DEV_TABLES.get(key)
+    if tab is None:
+        tab = _table_host(o, n, lowpass_filter_width, rolloff).to(device)
+        _DEV_TABLES[key] = tab
+    return tab
+
+
+class _ResampleFn(torch.autograd.Function):
+    """y = K x on sel_resample, gx = K^T gy on sel_resample_bwd (same plan, same table)."""
+
+    @staticmethod
+    def forward(ctx, waveform, o, n, lowpass_filter_width, rolloff):
+        lib = L.lib()
+        tab = _table_dev(o, n, lowpass_filter_width, rolloff, waveform.device)
+        shape = waveform.shape
+        x = waveform.reshape(-1, shape[-1]).float().contiguous()
+        out_len = lib.sel_resample_out_len(x.shape[1], o, n)
+        y = torch.empty(x.shape[0], out_len, dtype=torch.float32, device=x.device)
+        L.call("sel_resample", L.ptr(x), x.shape[0], x.shape[1], o, n, lowpass_filter_width, rolloff, L.ptr(tab),
+               L.ptr(y), L.stream())
+        ctx.cfg = (o, n, lowpass_filter_width, rolloff, tab, shape, waveform.dtype)
+        return y.view(*shape[:-1], out_len)
+
+    @staticmethod
+    def backward(ctx, gy):
+        o, n, lowpass_filter_width, rolloff, tab, shape, dtype = ctx.cfg
+        g = gy.reshape(-1, gy.shape[-1]).float().contiguous()
+        gx = torch.empty(g.shape[0], shape[-1], dtype=torch.float32, device=g.device)
+        L.call("sel_resample_bwd", L.ptr(g), g.shape[0], shape[-1], o, n, lowpass_filter_width, rolloff, L.ptr(tab),
+               L.ptr(gx), L.stream())
+        return gx.view(shape).to(dtype), None, None, None, None
+
+
 def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99,
-             resampling_method="sinc_interp_hann"):
+             resampling_method="sinc_interp_hann", differentiable=False):
     """Drop-in for torchaudio.functional.resample (sinc_interp_hann): (..., time)
-    fp32 on the device -> (..., ceil(time * new / orig)) with the reduced ratio."""
+    fp32 on the device -> (..., ceil(time * new / orig)) with the reduced ratio.
+    differentiable=True (not in torchaudio's signature): the result carries the
+    gradient to `waveform` through sel_resample_bwd; the default has no backward."""
     if resampling_method not in ("sinc_interp_hann", "sinc_interpolation"):
         raise NotImplementedError(f"sel.resample: {resampling_method} is not implemented")
     if orig_freq <= 0 or new_freq <= 0:
@@ -39,11 +76,9 @@ def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99
     lib = L.lib()
     g = math.gcd(int(orig_freq), int(new_freq))
     o, n = int(orig_freq) // g, int(new_freq) // g
-    key = (o, n, int(lowpass_filter_width), float(rolloff), waveform.device)
-    tab = _DEV_TABLES.get(key)
-    if tab is None:
-        tab = _table_host(o, n, int(lowpass_filter_width), float(rolloff)).to(waveform.device)
-        _DEV_TABLES[key] = tab
+    if differentiable:
+        return _ResampleFn.apply(waveform, o, n, int(lowpass_filter_width), float(rolloff))
+    tab = _table_dev(o, n, int(lowpass_filter_width), float(rolloff), waveform.device)
     shape = waveform.shape
     x = waveform.reshape(-1, shape[-1]).float().contiguous()
     out_len = lib.sel_resample_out_len(x.shape[1], o, n)

@@ -36,7 +36,7 @@ from torch import nn
 
 from dataloader.data_utils import add_noise, set_epoch
 from losses import (DiscriminatorAdversarialLoss, FeatureMatchLoss, GeneratorAdversarialLoss,
-                    MultiMelSpectrogramLoss)
+                    MultiMelSpectrogramLoss, STOILoss)
 from models.autoencoder_without_PQC.AudioDec import Generator as GeneratorAudioDec
 from models.vocoder.HiFiGAN import Discriminator as DiscriminatorHiFiGAN
 from models.vocoder.modules.discriminator import frozen_parameters
@@ -81,12 +81,26 @@ def _unwrap(m):
 
 class DenoiseStep:
     """model_step + calculate_generator_loss / calculate_discriminator_loss of
-    train_denoise.py:138-165, :213-263 (GAN mode once ``discriminator_enabled``)."""
+    train_denoise.py:138-165, :213-263 (GAN mode once ``discriminator_enabled``).
+
+    Not in the reference: ``config["lambda_stoi_loss"]`` (absent or 0: nothing
+    runs and the record tuple is unchanged) adds ``lambda * STOILoss(
+    config["sampling_rate"], config.get("stoi_loss_extended", False))(pred,
+    target)`` to the generator loss and ``("stoi_loss", ...)`` to the records.
+    Under a process group the recorded value is rank-local, like the eval
+    scalars; the term is linear in the per-rank means, so DDP's gradient
+    averaging gives the exact gradient of the global-batch term for equal
+    shards, and no all-reduce is added."""
 
     def __init__(self, config, device, generator=None, optimizer=None, discriminator=None,
                  disc_optimizer=None):
         self.config = config
         self.device = device
+        self.stoi_loss = None
+        if config.get("lambda_stoi_loss", 0.0):
+            if "sampling_rate" not in config:
+                raise KeyError("lambda_stoi_loss needs config['sampling_rate'] (the rate of the training waveforms)")
+            self.stoi_loss = STOILoss(config["sampling_rate"], config.get("stoi_loss_extended", False))
         self.model = {"generator": generator if generator is not None
                       else GeneratorAudioDec(**config["generator_params"]).to(device),
                       "discriminator": discriminator}
@@ -152,8 +166,13 @@ class DenoiseStep:
                     p = Dm(target)
             adv_loss = c["lambda_adv"] * self.criterion["gen_adv"](pred)  # :147 passes the waveform (quirk)
             feat_loss = c["lambda_feat_match"] * self.criterion["feat_match"](p_, p)
-        return mel_loss + adv_loss + feat_loss + snr_loss, (("mel_loss", mel_loss), ("adv_loss", adv_loss),
-                                                            ("feat_loss", feat_loss), ("snr_loss", snr_loss))
+        total = mel_loss + adv_loss + feat_loss + snr_loss
+        records = (("mel_loss", mel_loss), ("adv_loss", adv_loss), ("feat_loss", feat_loss), ("snr_loss", snr_loss))
+        if self.stoi_loss is not None:
+            stoi_loss = c["lambda_stoi_loss"] * self.stoi_loss(pred, target)
+            total = total + stoi_loss
+            records += (("stoi_loss", stoi_loss),)
+        return total, records
 
     def calculate_discriminator_loss(self, pred, target):
         """:157-165, with D(target) and D(pred) as ONE pass over the concatenated

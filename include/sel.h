@@ -728,6 +728,26 @@ int sel_stoi(const float* clean, const float* proc, int64_t B, int64_t T, int ex
              float* mean /*1, may be NULL*/, int* info /*3B, may be NULL*/, void* ws, size_t ws_bytes,
              sel_stream_t stream);
 int sel_stoi_band_edges(int* edges /*16*/);
+/* Gradient of STOI / ESTOI with respect to the processed signal;
+ * the clean signal is data.  g_proc (B, T) = d(sum_b g_d[b] d[b] + g_mean[0]
+ * mean) / d proc, i.e. row b is scaled by g_row = g_d[b] + g_mean[0] / B; either
+ * of g_d (B) / g_mean (1) may be null, not both.  ws_fwd is the workspace that
+ * sel_stoi filled for the same (clean, proc, B, T): the kept-frame lists, the
+ * counts and the band magnitudes are read from it and it is not written.
+ * ws_bwd: sel_stoi_bwd_workspace(B, T) bytes, 8-byte aligned like ws_fwd.
+ * The silent-frame mask is a constant selection (no gradient flows through it).
+ * The STOI clip min(c y, beta x) takes the c y branch (c depends on y) where
+ * c y < beta x and is a constant otherwise (c still depends on y in the other
+ * cells of that band).  Exactly 0: the cells of a band magnitude that is exactly
+ * 0; every sample of a row with M < 30 (its d is the constant 1e-5); samples
+ * that no kept frame covers; the tail past the last frame.  Every element of
+ * g_proc is written by the call.  fp64 inside, no atomics: the same bits run
+ * to run.  Refusals as sel_stoi, plus a null g_proc, g_d and g_mean both null
+ * and a workspace that is not 8-byte aligned (SEL_ERR_ARG). */
+size_t sel_stoi_bwd_workspace(int64_t B, int64_t T);
+int sel_stoi_bwd(const float* clean, const float* proc, int64_t B, int64_t T, int extended,
+                 const float* g_d /*B, may be NULL*/, const float* g_mean /*1, may be NULL*/, float* g_proc /*(B, T)*/,
+                 const void* ws_fwd, size_t ws_fwd_bytes, void* ws_bwd, size_t ws_bwd_bytes, sel_stream_t stream);
 /* BSS-eval SDR: torchmetrics 1.2.0 signal_distortion_ratio with the
  * direct solve, over the last dim of (B, T) fp32, L = filter_length in [1, 512],
  * B <= 65535, T <= 2^32.  In fp64: subtract each row's mean (zero_mean),
@@ -760,6 +780,12 @@ int64_t sel_resample_out_len(int64_t len, int orig_freq, int new_freq);
 int sel_resample_kernel(int orig_freq, int new_freq, int lowpass_filter_width, float rolloff, float* table);
 int sel_resample(const float* x, int64_t n_wavs, int64_t len, int orig_freq, int new_freq, int lowpass_filter_width,
                  float rolloff, const float* table, float* y, sel_stream_t stream);
+/* The transpose of sel_resample for the same plan and table: gy (n_wavs,
+ * sel_resample_out_len(len, ...)) -> gx (n_wavs, len) = K^T gy.  One thread per
+ * input sample gathers its output frames and phases in ascending order (no
+ * atomics); every element of gx is written.  Refusals as sel_resample. */
+int sel_resample_bwd(const float* gy, int64_t n_wavs, int64_t len, int orig_freq, int new_freq,
+                     int lowpass_filter_width, float rolloff, const float* table, float* gx, sel_stream_t stream);
 
 /* ---- waveform shape loss (losses/waveform_loss.py:15-74), one window length per call ----
  * L1(maxpool_w(|y_hat|), maxpool_w(|y|)) over (rows, T) -> out[0]; argidx/dsign
