@@ -1,5 +1,6 @@
-// Helpers shared by the conv-stack translation units (conv.hip, conv_wss.hip,
-// conv_pack.hip).
+// Helpers and cross-file declarations shared by the conv-stack translation
+// units (conv.hip, conv_ru.hip, conv_wgrad.hip, conv_wss.hip, conv_pack.hip);
+// the kernel helpers that only the first three share are in conv_tile.h.
 #pragma once
 #include "sel_common.h"
 
@@ -108,6 +109,15 @@ namespace conv {
 // conv.hip: descriptor check and its kernel-argument form
 int check_desc(const sel_conv_desc* d);
 Args to_args(const sel_conv_desc* d);
+// conv.hip: variant of a bf16 forward launch on the pipelined kernels (21-30), or -1
+int fwd4_choice(const Args& a, bool out_f32);
+// conv.hip: discriminator layers (dconv.hip) on the warp-specialised kernels
+int dconv_ws_fwd(const sel_dconv_desc* d, const void* x, const void* wp, const float* bias, const void* aux,
+                 const void* res, void* out, hipStream_t s);
+// -1: shape not supported there, 0: per-sequence tiles, 1: flat tiles across sequences
+int dconv_ws_mode(const sel_dconv_desc* d);
+// true: dconv_ws_fwd runs the shape on the eight-wave 256 x 256 kernel (k_conv_ws8)
+bool dconv_ws8_ok(const sel_dconv_desc* d);
 // conv_wss.hip: sample-tile warp-specialised kernel (T <= 400)
 bool wss_geometry(const Args& a, int& S, int& tm, int& BN);  // strips per tile, tile rows, channels
 bool wss_geometry(const Args& a, int& S, int& tm);

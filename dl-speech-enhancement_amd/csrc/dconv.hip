@@ -35,18 +35,9 @@
 //     weight-norm backward (torch.nn.utils.weight_norm, used by the MPD).
 #include <algorithm>
 
-#include "sel_common.h"
+#include "conv_common.h"  // dconv_ws_*: the layers that run on conv.hip's warp-specialised kernels
 
 namespace sel {
-namespace conv {
-// conv.hip: discriminator layers on the generator's warp-specialised kernel
-int dconv_ws_fwd(const sel_dconv_desc* d, const void* x, const void* wp, const float* bias, const void* aux,
-                 const void* res, void* out, hipStream_t s);
-// -1: shape not supported there, 0: per-sequence tiles, 1: flat tiles across sequences
-int dconv_ws_mode(const sel_dconv_desc* d);
-// true: dconv_ws_fwd runs the shape on the eight-wave 256 x 256 kernel (k_conv_ws8)
-bool dconv_ws8_ok(const sel_dconv_desc* d);
-}  // namespace conv
 namespace dconv {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));

@@ -679,7 +679,7 @@ RU_FUSED = os.environ.get("SEL_RU_FUSED", "")
 
 
 def _ru_shape_ok(d1, dtype):
-    """Mirror of the C side's eligibility (conv.hip ru_fused_ok)."""
+    """Mirror of the C side's eligibility (conv_ru.hip ru_fused_ok)."""
     return (dtype == torch.bfloat16 and d1.C == d1.N and d1.C in (32, 64) and d1.K == 7
             and d1.pad == 6 * d1.dil and d1.pad_mode == PAD_ZERO and d1.in_elu == 1 and 6 * d1.dil <= 64
             and d1.bias_period in (0, d1.N))
@@ -696,7 +696,7 @@ WSS_PW_KID = 94 * 10 ** 7 + 128 * 10 ** 4 + 16 * 10 + 7   # k_conv_wss<7, 16, 12
 
 def ru128_fused_ok(d1, dtype):
     """The 128-channel unit's forward as one k_conv_wss launch with the 1x1 in
-    its epilogue (conv_wss.hip PW, conv.hip sel_resunit_fwd): where conv1 itself
+    its epilogue (conv_wss.hip PW, conv_ru.hip sel_resunit_fwd): where conv1 itself
     runs on the (16, 128) tile; tune key 69 = 1 turns it off."""
     if not (RU_FUSED != "0" and dtype == torch.bfloat16 and d1.C == d1.N == 128 and d1.K == 7
             and d1.pad == 6 * d1.dil and d1.pad_mode == PAD_ZERO and d1.in_elu == 1

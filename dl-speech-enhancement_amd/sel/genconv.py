@@ -33,7 +33,7 @@ import torch.nn.functional as F
 
 from . import convops as CO
 
-_WG_TAPS = 8   # sel_conv_wgrad: K <= 8 (conv.hip wgrad_impl)
+_WG_TAPS = 8   # sel_conv_wgrad: K <= 8 (conv_wgrad.hip wgrad_impl)
 
 
 class Stride1Fn(torch.autograd.Function):

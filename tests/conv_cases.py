@@ -1,6 +1,6 @@
 """Cases, fp64 references and bounds of the 1-D conv primitive (csrc/conv.hip,
-csrc/conv_wss.hip: sel_conv_fwd / sel_conv_wgrad) at its tile and dispatch
-edges, shared by tests/test_gpu_conv_edges.py, tests/test_conv_cases_host.py
+csrc/conv_wss.hip, csrc/conv_wgrad.hip: sel_conv_fwd / sel_conv_wgrad) at its
+tile and dispatch edges, shared by tests/test_gpu_conv_edges.py, tests/test_conv_cases_host.py
 and tests/test_gpu_c3.py (which takes its operands, reference and bf16 checker
 from here).  Nothing here needs a GPU: sel_conv_fwd_kernel_id and
 sel_conv_wgrad_workspace are host decisions.
@@ -17,7 +17,7 @@ What lives here:
   * NOT_WSS: the neighbours of k_conv_wss's legal shapes that must not reach it;
   * WGRAD_CASES: weight-gradient launches with the plan they must get (mode,
     k_wgrad3_bf16 instance, tiles per split, number of splits), and
-    wgrad_mode / wgrad_plan / wgrad_workspace: conv.hip's plan restated;
+    wgrad_mode / wgrad_plan / wgrad_workspace: conv_wgrad.hip's plan restated;
   * operands / reference / wgrad_reference: the buffers of a case and the fp64
     primitive on the same rounded operands, with the sums of absolute terms the
     fp32 bounds scale with;
@@ -74,7 +74,7 @@ BF16, F32 = torch.bfloat16, torch.float32
 OUT_FILL = 7.0          # prefill of output buffers
 GUARD = 4096            # guard elements after an output buffer
 
-# constants of conv.hip, restated
+# constants of conv_wgrad.hip and conv_tile.h, restated
 W2_BM, W2_HALO, WB_BM, WB_BC, WG_BM = 128, 64, 64, 32, 64
 C1_TR, C1_NMAX, C1_KMAX, C1_HALO = 256, 64, 8, 64
 WF_BM, WF_XR, SPLIT_GROUP = 64, 128, 32
@@ -442,7 +442,7 @@ def mutate(case, ops, ref, how):
 
 
 # ---------------------------------------------------------------------------
-# weight gradient: conv.hip's wgrad_mode / wgrad_plan restated, cases
+# weight gradient: conv_wgrad.hip's wgrad_mode / wgrad_plan restated, cases
 # ---------------------------------------------------------------------------
 def _cdiv(a, b):
     return -(-a // b)
@@ -492,7 +492,7 @@ def wgrad3_reachable():
 
 
 def wgrad_plan(d, mode, tune=None):
-    """dict(mode, inst, bn, n_tiles, tiles_per_split, nsplit) as conv.hip plans it."""
+    """dict(mode, inst, bn, n_tiles, tiles_per_split, nsplit) as conv_wgrad.hip plans it."""
     tune = tune or {}
     B = d.rows // d.T
     if mode == 4:
@@ -534,7 +534,7 @@ def wgrad_workspace(d):
 
 
 def wgrad_kernel(d, bf16, tune=None):
-    """Name of the partial kernel a weight-gradient launch runs (conv.hip wgrad_impl)."""
+    """Name of the partial kernel a weight-gradient launch runs (conv_wgrad.hip wgrad_impl)."""
     tune = tune or {}
     p = wgrad_plan(d, wgrad_mode(d, bf16, tune), tune)
     t = "bf16" if bf16 else "float"
@@ -675,7 +675,7 @@ def wgrad_reference(case, g, x):
 
 def unpack_ref(kind, gwp, cout, cin, k, stride):
     """Packed (N, K, C) gradient -> the torch weight layout, index by index as
-    conv.hip's pack_dst maps it (structural zeros of the strided form dropped)."""
+    conv_wgrad.hip's pack_dst maps it (structural zeros of the strided form dropped)."""
     flat = gwp.reshape(-1)
     j = torch.arange(flat.numel(), device=flat.device)
     if kind == CO.PACK_FWD:

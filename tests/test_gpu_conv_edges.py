@@ -1,5 +1,5 @@
-"""The 1-D conv primitive (csrc/conv.hip, csrc/conv_wss.hip) against fp64 at its
-tile and dispatch edges: every case of tests/conv_cases.py through sel_conv_fwd
+"""The 1-D conv primitive (csrc/conv.hip, csrc/conv_wss.hip and its weight
+gradients, csrc/conv_wgrad.hip) against fp64 at its tile and dispatch edges: every case of tests/conv_cases.py through sel_conv_fwd
 in each of its output dtypes with its epilogue operands, and every
 weight-gradient case through sel_conv_wgrad (or sel_conv_wgrad_unpacked), each
 held element by element to the bounds derived in that module's docstring.  A
