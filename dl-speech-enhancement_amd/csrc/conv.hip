@@ -2188,7 +2188,7 @@ int dispatch_fwd(const Args& a, const void* in, const void* wp, const float* bia
 
 }  // namespace
 
-// Discriminator layers (dconv.hip, sel_dconv_desc) on the warp-specialised
+// Discriminator layers (dconv.hip's plan_fwd, sel_dconv_desc) on the warp-specialised
 // 256 x 128 kernel: one group, a contiguous reduction row (S == 1 or Cs == Cg:
 // the phase view of a strided layer is S * Cg contiguous channels), contiguous
 // output columns, K in {2, 3, 5, 7}.  The MPD's (5,1) convs are K = 5 (stride 1)

@@ -111,7 +111,7 @@ int check_desc(const sel_conv_desc* d);
 Args to_args(const sel_conv_desc* d);
 // conv.hip: variant of a bf16 forward launch on the pipelined kernels (21-30), or -1
 int fwd4_choice(const Args& a, bool out_f32);
-// conv.hip: discriminator layers (dconv.hip) on the warp-specialised kernels
+// conv.hip: discriminator layers (dconv.hip's plan_fwd) on the warp-specialised kernels
 int dconv_ws_fwd(const sel_dconv_desc* d, const void* x, const void* wp, const float* bias, const void* aux,
                  const void* res, void* out, hipStream_t s);
 // -1: shape not supported there, 0: per-sequence tiles, 1: flat tiles across sequences

@@ -1,6 +1,7 @@
 // Device code that more than one of the conv kernel files (conv.hip,
-// conv_ru.hip, conv_wgrad.hip) uses; only those three include it.  What a
-// single file uses stays in that file.
+// conv_ru.hip, conv_wgrad.hip) uses; only those three include it, and
+// dconv_wgrad.hip for tr_read / tr_frag.  What a single file uses stays in
+// that file.
 #pragma once
 #include "conv_common.h"
 
@@ -168,8 +169,9 @@ __device__ __forceinline__ float c1_act(float v) {
 }
 
 // Transposing LDS reads (ds_read_b64_tr_b16, 4 rows x 16 columns per 16-lane
-// group): the MFMA operands of the bf16 weight gradients, which reduce over the
-// ROW index of row-major LDS tiles (k_wgrad_bf16's comment has the layout).
+// group): the MFMA operands of the bf16 weight gradients (the discriminator's
+// in dconv_wgrad.hip too), which reduce over the ROW index of row-major LDS
+// tiles (k_wgrad_bf16's comment has the layout).
 typedef short v4i16 __attribute__((ext_vector_type(4)));
 typedef short v8i16 __attribute__((ext_vector_type(8)));
 

@@ -1,4 +1,5 @@
-"""Autograd ops over the HiFi-GAN discriminator kernels of libsel.so (dconv.hip).
+"""Autograd ops over the HiFi-GAN discriminator kernels of libsel.so (dconv.hip,
+dconv_wgrad.hip, dconv_pack.hip; the front-end and loss kernels of gan.hip).
 
 A sub-discriminator (one HiFiGANScaleDiscriminator or HiFiGANPeriodDiscriminator,
 models/vocoder/modules/discriminator.py:26-372) is a chain of convs with

@@ -1,5 +1,6 @@
 """Cases, fp64 references and bounds of the discriminator conv kernels
-(csrc/dconv.hip and its hand-off to conv.hip's warp-specialised kernels),
+(csrc/dconv.hip and its hand-off to conv.hip's warp-specialised kernels,
+csrc/dconv_wgrad.hip, csrc/dconv_pack.hip),
 shared by tests/test_gpu_dconv_edges.py and tests/test_dconv_cases_host.py, and
 the bf16 checker tests/test_gpu_gan.py and tests/test_gpu_dconv_variants.py use.
 Nothing here needs a GPU: the library's dispatch reporters run on the host.
@@ -17,7 +18,7 @@ What lives here:
     the fp64 torch conv1d of the layer on the same rounded operands, its
     autograd for the adjoint and the weight / bias gradients, and the sums of
     absolute products the fp32 bounds scale with;
-  * wg_plan: the weight-gradient plan of dconv.hip restated;
+  * wg_plan: the weight-gradient plan of dconv_wgrad.hip restated;
   * pack_ref / prim_ref: the pack order and the primitive's formula
     (include/sel.h) restated index by index, for the host test that ties the
     layer view to the descriptor view.
@@ -67,7 +68,7 @@ GAP_FILL = 1.0e3       # finite garbage in input gap rows and pad columns
 OUT_FILL = 7.0         # prefill of the output buffers
 WG_NORM_ROWS = 4096    # rows up to which the weight gradient is held to 1e-5 norm-wise
 
-# the constants of dconv.hip / sel_common.h, restated
+# the constants of dconv_wgrad.hip / sel_common.h, restated
 W3_BM, WG_BM, WG_TAPS, PRESUM = 128, 64, 8, 16
 WG_CAP = 64 << 20
 RU_OOB = 0x7FFFFFF0
@@ -477,7 +478,7 @@ def wgrad_norm_limit(rows, plain_fp32_err):
 
 
 # ---------------------------------------------------------------------------
-# wg_plan of dconv.hip, restated
+# wg_plan of dconv_wgrad.hip, restated
 # ---------------------------------------------------------------------------
 _SHORT_KR = (2, 3, 6, 15)
 _DWSX = ((15, 1), (2, 3), (3, 1), (2, 1), (6, 1), (1, 2), (1, 3))

@@ -1,5 +1,5 @@
-"""The discriminator conv kernels (csrc/dconv.hip, and conv.hip's warp-specialised
-kernels behind dconv_ws_fwd) against fp64 torch at their dispatch edges: every
+"""The discriminator conv kernels (csrc/dconv.hip, csrc/dconv_wgrad.hip, and
+conv.hip's warp-specialised kernels behind dconv_ws_fwd) against fp64 torch at their dispatch edges: every
 case of tests/dconv_cases.py x {bf16, fp32} through the forward (bias +
 LeakyReLU), the adjoint (plain, and with (+ res) * LeakyReLU'(aux)) and the
 weight / bias gradient, each held to the bounds derived in that module's

@@ -1,6 +1,7 @@
 """GPU parity of GAN mode (BASELINE config C5): the HiFi-GAN
 MSD + MPD discriminator (models/vocoder/HiFiGAN.py:308-395), the adversarial
-and feature-matching losses, and the discriminator conv kernels (dconv.hip).
+and feature-matching losses (gan.hip), and the discriminator conv kernels
+(dconv.hip, dconv_wgrad.hip, dconv_pack.hip).
 
 Goldens (tests/golden/discriminator.npz, gan_step.npz) come from the reference
 itself at reduced width (make_goldens.py --only gan).  Tolerances: fp32 path
