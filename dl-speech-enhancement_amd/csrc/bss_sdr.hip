@@ -25,13 +25,24 @@ namespace bss {
 constexpr int kMaxTaps = 512;
 constexpr int kChunk = 2048;  // samples of n per correlation block
 
+// Ragged batches: row b is its first lengths[b] samples, T stays the
+// row stride.  A length above T counts as T, a negative one as 0.
+__device__ __forceinline__ int64_t row_len(const int64_t* __restrict__ lens, int64_t b, int64_t T) {
+  const int64_t n = lens[b];
+  return n > T ? T : (n < 0 ? 0 : n);
+}
+
 // One block per row: the two means in fp64 (launched only with zero_mean).
-__global__ __launch_bounds__(256) void k_bss_means(const float* __restrict__ p, const float* __restrict__ t, int64_t T,
+template <bool VAR>
+__global__ __launch_bounds__(256) void k_bss_means(const float* __restrict__ p, const float* __restrict__ t,
+                                                   int64_t stride, const int64_t* __restrict__ lens,
                                                    double* __restrict__ means) {
   __shared__ double red[16];
   const int64_t b = blockIdx.x;
-  const float* __restrict__ pr = p + b * T;
-  const float* __restrict__ tr = t + b * T;
+  const float* __restrict__ pr = p + b * stride;
+  const float* __restrict__ tr = t + b * stride;
+  int64_t T = stride;  // the row's own length
+  if constexpr (VAR) T = row_len(lens, b, stride);
   double sp = 0.0, st = 0.0;
   for (int64_t i = threadIdx.x; i < T; i += blockDim.x) {
     sp += double(pr[i]);
@@ -54,18 +65,33 @@ __global__ __launch_bounds__(256) void k_bss_means(const float* __restrict__ p, 
 // the wave passes them round with v_readlane (as an LDS broadcast read per n
 // they would cost half as many LDS cycles again as the pairs do).  The loop
 // runs to the next multiple of 64 past the chunk's end: t[n] is 0 there.
-// part: (B, chunks, 2L + 1) = r, b, sum p^2.
+// part: (B, chunks, 2L + 1) = r, b, sum p^2.  With lengths a chunk that starts at
+// or past the row's end writes zero partials (the solve sums every chunk).
+template <bool VAR>
 __global__ __launch_bounds__(kMaxTaps) void k_bss_corr(const float* __restrict__ p, const float* __restrict__ t,
-                                                       int64_t T, int L, const double* __restrict__ means,
-                                                       double* __restrict__ part) {
+                                                       int64_t stride, const int64_t* __restrict__ lens, int L,
+                                                       const double* __restrict__ means, double* __restrict__ part) {
   __shared__ double2 s[kChunk + kMaxTaps];  // .x = t, .y = p
   __shared__ double red[16];
   const int64_t b = blockIdx.y;
   const int64_t n0 = int64_t(blockIdx.x) * kChunk;
   const int tid = threadIdx.x, lane = tid & 63;
+  int64_t T = stride;  // the row's own length
+  if constexpr (VAR) {
+    T = row_len(lens, b, stride);
+    if (n0 >= T) {  // block-uniform
+      double* __restrict__ z = part + (b * gridDim.x + blockIdx.x) * int64_t(2 * L + 1);
+      if (tid < L) {
+        z[tid] = 0.0;
+        z[L + tid] = 0.0;
+      }
+      if (tid == 0) z[2 * L] = 0.0;
+      return;
+    }
+  }
   const double mp = means ? means[2 * b] : 0.0, mt = means ? means[2 * b + 1] : 0.0;
-  const float* __restrict__ pr = p + b * T;
-  const float* __restrict__ tr = t + b * T;
+  const float* __restrict__ pr = p + b * stride;
+  const float* __restrict__ tr = t + b * stride;
   for (int i = tid; i < kChunk + kMaxTaps; i += blockDim.x) {
     const int64_t g = n0 + i;
     double2 v = {0.0, 0.0};
@@ -110,8 +136,10 @@ __global__ __launch_bounds__(kMaxTaps) void k_bss_corr(const float* __restrict__
 //   k = -(r[m] + sum_{1 <= i < m} a[i] r[m - i]) / E,  a[i] += k a[m - i],  a[m] = k,  E *= 1 - k^2
 //   q = (b[m] - sum_{i < m} x[i] r[m - i]) / E,         x[i] += q a[m - i],  x[m] = q
 // Both sums use only the state of the step before, so they share one reduction.
+template <bool VAR>
 __global__ __launch_bounds__(kMaxTaps) void k_bss_solve(const double* __restrict__ part, int chunks, int L,
-                                                        double load_diag, double* __restrict__ corr,
+                                                        double load_diag, int64_t T,
+                                                        const int64_t* __restrict__ lens, double* __restrict__ corr,
                                                         double* __restrict__ dvals, float* __restrict__ vals) {
   __shared__ double r[kMaxTaps], bv[kMaxTaps];
   __shared__ double abuf[2][kMaxTaps];
@@ -182,6 +210,9 @@ __global__ __launch_bounds__(kMaxTaps) void k_bss_solve(const double* __restrict
     double v = 10.0 * log10(coh / (1.0 - coh));
     if (1.0 - coh <= 0.0) v = INFINITY;
     if (!(r0 > 0.0)) v = NAN;  // silent target
+    if constexpr (VAR) {
+      if (row_len(lens, row, T) < 1) v = NAN;  // an empty row (r0 may be load_diag alone)
+    }
     dvals[row] = v;
     vals[row] = float(v);
   }
@@ -216,20 +247,23 @@ size_t sel_bss_sdr_workspace(int64_t B, int64_t T, int filter_length) {
   return size_t(B) * (3 + size_t(chunks_of(T)) * size_t(2 * filter_length + 1)) * sizeof(double);
 }
 
-int sel_bss_sdr(const float* pred, const float* target, int64_t B, int64_t T, int filter_length, int zero_mean,
-                double load_diag, float* vals, float* mean, double* corr, void* ws, size_t ws_bytes,
-                sel_stream_t stream) {
-  SEL_REQUIRE(pred && target && vals && ws, SEL_ERR_ARG, "sel_bss_sdr: null pointer");
-  SEL_REQUIRE(B > 0 && B <= 65535, SEL_ERR_ARG, "sel_bss_sdr: B must be in [1, 65535]");
-  SEL_REQUIRE(T > 0 && T <= (int64_t(1) << 32), SEL_ERR_ARG, "sel_bss_sdr: T must be in [1, 2^32]");
-  SEL_REQUIRE(filter_length >= 1 && filter_length <= kMaxTaps, SEL_ERR_ARG,
-              "sel_bss_sdr: filter_length must be in [1, %d]", kMaxTaps);
-  SEL_REQUIRE((zero_mean | 1) == 1, SEL_ERR_ARG, "sel_bss_sdr: zero_mean must be 0 or 1");
+namespace {
+
+// sel_bss_sdr and sel_bss_sdr_var: lens == nullptr is the fixed-length call
+int bss_sdr(const char* fn, const float* pred, const float* target, int64_t B, int64_t T, const int64_t* lens,
+            int filter_length, int zero_mean, double load_diag, float* vals, float* mean, double* corr, void* ws,
+            size_t ws_bytes, sel_stream_t stream) {
+  SEL_REQUIRE(pred && target && vals && ws, SEL_ERR_ARG, "%s: null pointer", fn);
+  SEL_REQUIRE(B > 0 && B <= 65535, SEL_ERR_ARG, "%s: B must be in [1, 65535]", fn);
+  SEL_REQUIRE(T > 0 && T <= (int64_t(1) << 32), SEL_ERR_ARG, "%s: T must be in [1, 2^32]", fn);
+  SEL_REQUIRE(filter_length >= 1 && filter_length <= kMaxTaps, SEL_ERR_ARG, "%s: filter_length must be in [1, %d]",
+              fn, kMaxTaps);
+  SEL_REQUIRE((zero_mean | 1) == 1, SEL_ERR_ARG, "%s: zero_mean must be 0 or 1", fn);
   SEL_REQUIRE(std::isfinite(load_diag) && load_diag >= 0.0, SEL_ERR_ARG,
-              "sel_bss_sdr: load_diag must be finite and not negative");
-  SEL_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, SEL_ERR_ARG, "sel_bss_sdr: workspace not 8-byte aligned");
-  SEL_REQUIRE(ws_bytes >= sel_bss_sdr_workspace(B, T, filter_length), SEL_ERR_WORKSPACE,
-              "sel_bss_sdr: workspace too small");
+              "%s: load_diag must be finite and not negative", fn);
+  SEL_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, SEL_ERR_ARG, "%s: workspace not 8-byte aligned", fn);
+  SEL_REQUIRE(ws_bytes >= sel_bss_sdr_workspace(B, T, filter_length), SEL_ERR_WORKSPACE, "%s: workspace too small",
+              fn);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int L = filter_length;
   const int threads = (L + 63) / 64 * 64;
@@ -237,15 +271,28 @@ int sel_bss_sdr(const float* pred, const float* target, int64_t B, int64_t T, in
   double* means = static_cast<double*>(ws);
   double* dvals = means + 2 * B;
   double* part = dvals + B;
-  if (zero_mean) {
-    hipLaunchKernelGGL(k_bss_means, dim3(unsigned(B)), dim3(256), 0, s, pred, target, T, means);
+  const double* cm = zero_mean ? means : static_cast<const double*>(nullptr);
+  if (lens) {
+    if (zero_mean) {
+      hipLaunchKernelGGL(k_bss_means<true>, dim3(unsigned(B)), dim3(256), 0, s, pred, target, T, lens, means);
+      SEL_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_bss_corr<true>, dim3(unsigned(chunks), unsigned(B)), dim3(threads), 0, s, pred, target, T,
+                       lens, L, cm, part);
     SEL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_bss_solve<true>, dim3(unsigned(B)), dim3(threads), 0, s, part, chunks, L, load_diag, T, lens,
+                       corr, dvals, vals);
+  } else {
+    if (zero_mean) {
+      hipLaunchKernelGGL(k_bss_means<false>, dim3(unsigned(B)), dim3(256), 0, s, pred, target, T, lens, means);
+      SEL_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(k_bss_corr<false>, dim3(unsigned(chunks), unsigned(B)), dim3(threads), 0, s, pred, target, T,
+                       lens, L, cm, part);
+    SEL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_bss_solve<false>, dim3(unsigned(B)), dim3(threads), 0, s, part, chunks, L, load_diag, T,
+                       lens, corr, dvals, vals);
   }
-  hipLaunchKernelGGL(k_bss_corr, dim3(unsigned(chunks), unsigned(B)), dim3(threads), 0, s, pred, target, T, L,
-                     zero_mean ? means : static_cast<const double*>(nullptr), part);
-  SEL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_bss_solve, dim3(unsigned(B)), dim3(threads), 0, s, part, chunks, L, load_diag, corr, dvals,
-                     vals);
   SEL_LAUNCH_CHECK();
   if (mean) {
     hipLaunchKernelGGL(k_bss_mean, dim3(1), dim3(256), 0, s, dvals, B, mean);
@@ -254,5 +301,21 @@ int sel_bss_sdr(const float* pred, const float* target, int64_t B, int64_t T, in
   return SEL_OK;
 }
 
-}  // extern "C"
+}  // namespace
 
+int sel_bss_sdr(const float* pred, const float* target, int64_t B, int64_t T, int filter_length, int zero_mean,
+                double load_diag, float* vals, float* mean, double* corr, void* ws, size_t ws_bytes,
+                sel_stream_t stream) {
+  return bss_sdr("sel_bss_sdr", pred, target, B, T, nullptr, filter_length, zero_mean, load_diag, vals, mean, corr, ws,
+                 ws_bytes, stream);
+}
+
+int sel_bss_sdr_var(const float* pred, const float* target, int64_t B, int64_t T, const int64_t* lengths,
+                    int filter_length, int zero_mean, double load_diag, float* vals, float* mean, double* corr,
+                    void* ws, size_t ws_bytes, sel_stream_t stream) {
+  SEL_REQUIRE(lengths, SEL_ERR_ARG, "sel_bss_sdr_var: null lengths");
+  return bss_sdr("sel_bss_sdr_var", pred, target, B, T, lengths, filter_length, zero_mean, load_diag, vals, mean, corr,
+                 ws, ws_bytes, stream);
+}
+
+}  // extern "C"

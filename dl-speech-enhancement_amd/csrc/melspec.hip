@@ -113,11 +113,18 @@ __device__ __forceinline__ void stockham_pass(const float2* src, float2* dst, in
   }
 }
 
+// VAR (ragged batches): row b is its first lens[b] samples (above
+// T counts as T).  The reflect pad mirrors about the row's own last sample, the
+// row has 1 + len / hop frames (written to frames[b]) and the frames past them
+// are written as zero; a row of at most n_fft / 2 samples cannot be padded: it
+// is NaN throughout and has 0 frames.  Nothing at or past lens[b] is read.
+template <bool VAR>
 __global__ __launch_bounds__(THREADS) void k_power_mel_fwd(const float* __restrict__ x, Args a, Plan plan,
                                                            const float* __restrict__ window,
                                                            const float* __restrict__ fb,
                                                            const int32_t* __restrict__ krange,
-                                                           float* __restrict__ out) {
+                                                           const int64_t* __restrict__ lens,
+                                                           float* __restrict__ out, int64_t* __restrict__ frames) {
   __shared__ float2 lds[FPB][2][MAXM + 8];
   __shared__ float spec[FPB][MAXM + 8];
   const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -127,7 +134,17 @@ __global__ __launch_bounds__(THREADS) void k_power_mel_fwd(const float* __restri
   const int64_t b = blockIdx.x / fpb_per_sig;
   const int f0 = int(blockIdx.x % fpb_per_sig) * FPB;
   const int f = f0 + w;
-  const bool active = f < a.F;
+  bool active = f < a.F;
+  int64_t len = a.T;  // the row's own length
+  bool row_ok = true;
+  if constexpr (VAR) {
+    len = lens[b];
+    len = len > a.T ? a.T : len;
+    row_ok = len > a.P;
+    const int64_t Fb = row_ok ? 1 + len / a.hop : 0;
+    active = active && f < Fb;
+    if (f0 == 0 && threadIdx.x == 0) frames[b] = Fb;
+  }
   const float* xs = x + b * a.T;
   float2* src = lds[w][0];
   float2* dst = lds[w][1];
@@ -138,8 +155,8 @@ __global__ __launch_bounds__(THREADS) void k_power_mel_fwd(const float* __restri
     float v0 = 0.f, v1 = 0.f;
     if (active) {
       const int w0 = 2 * m - a.left, w1 = w0 + 1;
-      if (w0 >= 0 && w0 < a.win) v0 = window[w0] * xs[reflect_index(base + 2 * m, a.T)];
-      if (w1 >= 0 && w1 < a.win) v1 = window[w1] * xs[reflect_index(base + 2 * m + 1, a.T)];
+      if (w0 >= 0 && w0 < a.win) v0 = window[w0] * xs[reflect_index(base + 2 * m, len)];
+      if (w1 >= 0 && w1 < a.win) v1 = window[w1] * xs[reflect_index(base + 2 * m + 1, len)];
     }
     src[m] = make_float2(v0, v1);
   }
@@ -185,6 +202,9 @@ __global__ __launch_bounds__(THREADS) void k_power_mel_fwd(const float* __restri
 #pragma unroll
       for (int q = 0; q < FPB; ++q) acc[q] = fmaf(spec[q][k], wgt, acc[q]);
     }
+    if constexpr (VAR) {
+      if (!row_ok) acc[0] = acc[1] = acc[2] = acc[3] = NAN;
+    }
     float* row = out + (b * a.n_mels + m) * a.F + f0;
     const bool vec = (f0 + FPB <= a.F) && ((reinterpret_cast<uintptr_t>(row) & 15) == 0);
     if (vec) {
@@ -217,20 +237,24 @@ using namespace sel::melspec;
 
 extern "C" {
 
-int sel_power_mel_fwd(const float* x, int64_t B, int64_t T, int n_fft, int hop, int win_length,
-                      const float* window, const float* fb, const int32_t* krange, int n_mels, float power,
-                      float* out, sel_stream_t stream) {
-  SEL_REQUIRE(initialized(), SEL_ERR_STATE, "sel_init() not called");
-  SEL_REQUIRE(x && window && fb && krange && out, SEL_ERR_ARG, "null pointer");
-  SEL_REQUIRE(B > 0 && T > 0 && hop > 0 && n_mels > 0, SEL_ERR_ARG, "bad sizes");
+namespace {
+
+// sel_power_mel_fwd and sel_power_mel_fwd_var: lens == nullptr is the fixed-length call
+int power_mel(const char* fn, const float* x, int64_t B, int64_t T, const int64_t* lens, int n_fft, int hop,
+              int win_length, const float* window, const float* fb, const int32_t* krange, int n_mels, float power,
+              float* out, int64_t* frames, sel_stream_t stream) {
+  SEL_REQUIRE(x && window && fb && krange && out, SEL_ERR_ARG, "%s: null pointer", fn);
+  SEL_REQUIRE(B > 0 && T > 0 && hop > 0 && n_mels > 0, SEL_ERR_ARG, "%s: bad sizes", fn);
   SEL_REQUIRE(n_fft >= 8 && n_fft % 2 == 0 && n_fft / 2 <= MAXM, SEL_ERR_UNSUPPORTED,
-              "n_fft %d: need an even size <= %d", n_fft, 2 * MAXM);
-  SEL_REQUIRE(win_length > 0 && win_length <= n_fft, SEL_ERR_ARG, "win_length %d > n_fft %d", win_length, n_fft);
-  SEL_REQUIRE(T > n_fft / 2, SEL_ERR_ARG, "reflect pad %d needs T > pad (T=%lld)", n_fft / 2, (long long)T);
-  SEL_REQUIRE(power > 0.f, SEL_ERR_UNSUPPORTED, "power must be > 0 (None = complex output not supported)");
+              "%s: n_fft %d: need an even size <= %d", fn, n_fft, 2 * MAXM);
+  SEL_REQUIRE(win_length > 0 && win_length <= n_fft, SEL_ERR_ARG, "%s: win_length %d > n_fft %d", fn, win_length,
+              n_fft);
+  SEL_REQUIRE(T > n_fft / 2, SEL_ERR_ARG, "%s: reflect pad %d needs T > pad (T=%lld)", fn, n_fft / 2, (long long)T);
+  SEL_REQUIRE(power > 0.f, SEL_ERR_UNSUPPORTED, "%s: power must be > 0 (None = complex output not supported)", fn);
   Plan plan;
-  SEL_REQUIRE(make_plan(n_fft / 2, plan), SEL_ERR_UNSUPPORTED, "n_fft/2 = %d has prime factors other than 2,3,5",
-              n_fft / 2);
+  SEL_REQUIRE(make_plan(n_fft / 2, plan), SEL_ERR_UNSUPPORTED, "%s: n_fft/2 = %d has prime factors other than 2,3,5",
+              fn, n_fft / 2);
+  SEL_REQUIRE(T / hop < (int64_t(1) << 30), SEL_ERR_ARG, "%s: too many frames", fn);
   Args a;
   a.B = B;
   a.T = T;
@@ -242,11 +266,35 @@ int sel_power_mel_fwd(const float* x, int64_t B, int64_t T, int n_fft, int hop, 
   a.n_mels = n_mels;
   a.power = power;
   const int64_t blocks = B * ((a.F + FPB - 1) / FPB);
-  SEL_REQUIRE(blocks < (int64_t(1) << 31), SEL_ERR_ARG, "batch too large");
-  hipLaunchKernelGGL(k_power_mel_fwd, dim3(unsigned(blocks)), dim3(THREADS), 0,
-                     reinterpret_cast<hipStream_t>(stream), x, a, plan, window, fb, krange, out);
+  SEL_REQUIRE(blocks < (int64_t(1) << 31), SEL_ERR_ARG, "%s: batch too large", fn);
+  SEL_REQUIRE(initialized(), SEL_ERR_STATE, "sel_init() not called");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (lens)
+    hipLaunchKernelGGL(k_power_mel_fwd<true>, dim3(unsigned(blocks)), dim3(THREADS), 0, s, x, a, plan, window, fb,
+                       krange, lens, out, frames);
+  else
+    hipLaunchKernelGGL(k_power_mel_fwd<false>, dim3(unsigned(blocks)), dim3(THREADS), 0, s, x, a, plan, window, fb,
+                       krange, lens, out, frames);
   SEL_LAUNCH_CHECK();
   return SEL_OK;
+}
+
+}  // namespace
+
+int sel_power_mel_fwd(const float* x, int64_t B, int64_t T, int n_fft, int hop, int win_length,
+                      const float* window, const float* fb, const int32_t* krange, int n_mels, float power,
+                      float* out, sel_stream_t stream) {
+  SEL_REQUIRE(initialized(), SEL_ERR_STATE, "sel_init() not called");
+  return power_mel("sel_power_mel_fwd", x, B, T, nullptr, n_fft, hop, win_length, window, fb, krange, n_mels, power,
+                   out, nullptr, stream);
+}
+
+int sel_power_mel_fwd_var(const float* x, int64_t B, int64_t T, const int64_t* lengths, int n_fft, int hop,
+                          int win_length, const float* window, const float* fb, const int32_t* krange, int n_mels,
+                          float power, float* out, int64_t* frames, sel_stream_t stream) {
+  SEL_REQUIRE(lengths && frames, SEL_ERR_ARG, "sel_power_mel_fwd_var: null pointer");
+  return power_mel("sel_power_mel_fwd_var", x, B, T, lengths, n_fft, hop, win_length, window, fb, krange, n_mels,
+                   power, out, frames, stream);
 }
 
 }  // extern "C"

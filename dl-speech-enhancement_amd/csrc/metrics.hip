@@ -18,17 +18,27 @@ constexpr double kEps = 2.220446049250313e-16;     // numpy.finfo(float64).eps (
 // sel_snr_fwd's sums), then (mean p, mean t, S_pt, S_pp) per row (4B doubles).
 // ---------------------------------------------------------------------------
 
+// Ragged batches: row b is its first lengths[b] samples, T stays the
+// row stride.  A length above T counts as T, a negative one as 0.
+__device__ __forceinline__ int64_t row_len(const int64_t* __restrict__ lens, int64_t b, int64_t T) {
+  const int64_t n = lens[b];
+  return n > T ? T : (n < 0 ? 0 : n);
+}
+
 // One block per row, fp64 sums; with zero_mean a first pass takes the means and
 // the second sums the centred values (moments of the raw values would lose the
 // residual under a DC offset).
-__global__ __launch_bounds__(256) void k_sdr_sums(const float* __restrict__ p, const float* __restrict__ t, int64_t T,
-                                                  int zero_mean, double* __restrict__ pairs,
-                                                  double* __restrict__ ext) {
+template <bool VAR>
+__global__ __launch_bounds__(256) void k_sdr_sums(const float* __restrict__ p, const float* __restrict__ t,
+                                                  int64_t stride, const int64_t* __restrict__ lens, int zero_mean,
+                                                  double* __restrict__ pairs, double* __restrict__ ext) {
   __shared__ double red[16];
   __shared__ double bc[2];
   const int64_t b = blockIdx.x;
-  const float* __restrict__ pr = p + b * T;
-  const float* __restrict__ tr = t + b * T;
+  const float* __restrict__ pr = p + b * stride;
+  const float* __restrict__ tr = t + b * stride;
+  int64_t T = stride;  // the row's own length
+  if constexpr (VAR) T = row_len(lens, b, stride);
   double mp = 0.0, mt = 0.0;
   if (zero_mean) {
     double sp = 0.0, st = 0.0;
@@ -84,15 +94,19 @@ __device__ __forceinline__ void sdr_ratio(double stt, double sdd, double spt, do
   den = (r > 0.0 ? r : 0.0) + kEps32;
 }
 
+template <bool VAR>
 __global__ __launch_bounds__(256) void k_sdr_finish(const double* __restrict__ pairs, const double* __restrict__ ext,
-                                                    int64_t B, int si, float* __restrict__ vals,
-                                                    float* __restrict__ mean) {
+                                                    int64_t B, int64_t T, const int64_t* __restrict__ lens, int si,
+                                                    float* __restrict__ vals, float* __restrict__ mean) {
   __shared__ double red[16];
   double acc = 0.0;
   for (int64_t b = threadIdx.x; b < B; b += blockDim.x) {
     double alpha, num, den;
     sdr_ratio(pairs[2 * b], pairs[2 * b + 1], ext[4 * b + 2], ext[4 * b + 3], si, alpha, num, den);
-    const double v = 10.0 * log10(num / den);
+    double v = 10.0 * log10(num / den);
+    if constexpr (VAR) {
+      if (row_len(lens, b, T) < 1) v = NAN;  // an empty row has no value
+    }
     vals[b] = float(v);
     acc += v;
   }
@@ -108,15 +122,54 @@ __global__ __launch_bounds__(256) void k_snr_rows(const double* __restrict__ sum
   if (b < B) vals[b] = 10.f * log10f((float(sums[2 * b]) + eps) / (float(sums[2 * b + 1]) + eps));
 }
 
+// The plain SNR (scale_invariant = zero_mean = 0) of a ragged batch, in the
+// arithmetic of sel_snr_fwd (k_snr_sums / k_snr_finish) and k_snr_rows.
+__global__ __launch_bounds__(256) void k_snr_sums_var(const float* __restrict__ p, const float* __restrict__ t,
+                                                      int64_t T, const int64_t* __restrict__ lens,
+                                                      double* __restrict__ sums) {
+  __shared__ double red[16];
+  const int64_t b = blockIdx.x;
+  const int64_t n = row_len(lens, b, T);
+  double st = 0.0, sd = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
+    const float tv = t[b * T + i], d = tv - p[b * T + i];
+    st += double(tv) * tv;
+    sd += double(d) * d;
+  }
+  st = block_sum<double>(st, red);
+  sd = block_sum<double>(sd, red);
+  if (threadIdx.x == 0) {
+    sums[2 * b] = st;
+    sums[2 * b + 1] = sd;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_snr_finish_var(const double* __restrict__ sums, int64_t B, int64_t T,
+                                                        const int64_t* __restrict__ lens, float* __restrict__ vals,
+                                                        float* __restrict__ mean) {
+  __shared__ float red[16];
+  const float eps = 1.1920928955078125e-07f;
+  float v = 0.f;
+  for (int64_t b = threadIdx.x; b < B; b += blockDim.x) {
+    float r = 10.f * log10f((float(sums[2 * b]) + eps) / (float(sums[2 * b + 1]) + eps));
+    if (row_len(lens, b, T) < 1) r = NAN;
+    vals[b] = r;
+    v += r;
+  }
+  v = block_sum<float>(v, red);
+  if (threadIdx.x == 0) mean[0] = v / float(B);
+}
+
 constexpr int kBwdChunk = 4096;  // elements of a row per block of the gradient kernel
 
 // g_pred = g_row * (ct * (t - mean t) + cp * (p - mean p)); the two coefficients
 // follow from d/dp of 10 log10(num / den)
+template <bool VAR>
 __global__ __launch_bounds__(256) void k_sdr_bwd(const float* __restrict__ p, const float* __restrict__ t, int64_t B,
-                                                 int64_t T, int cpr, int si, int zero_mean,
-                                                 const double* __restrict__ pairs, const double* __restrict__ ext,
-                                                 const float* __restrict__ g_vals, const float* __restrict__ g_mean,
-                                                 float* __restrict__ gp) {
+                                                 int64_t T, const int64_t* __restrict__ lens, int cpr, int si,
+                                                 int zero_mean, const double* __restrict__ pairs,
+                                                 const double* __restrict__ ext, const float* __restrict__ g_vals,
+                                                 const float* __restrict__ g_mean, float* __restrict__ gp) {
   const int64_t b = blockIdx.x / cpr;
   const int c = int(blockIdx.x % cpr);
   const double stt = pairs[2 * b], sdd = pairs[2 * b + 1];
@@ -140,8 +193,30 @@ __global__ __launch_bounds__(256) void k_sdr_bwd(const float* __restrict__ p, co
   ct *= g;
   cp *= g;
   const int64_t i1 = int64_t(c + 1) * kBwdChunk < T ? int64_t(c + 1) * kBwdChunk : T;
+  if constexpr (VAR) {  // exact zeros at and past the row's length; nothing there is read
+    const int64_t n = row_len(lens, b, T);
+    for (int64_t i = int64_t(c) * kBwdChunk + threadIdx.x; i < i1; i += blockDim.x)
+      gp[b * T + i] = i < n ? float(ct * (double(t[b * T + i]) - mt) + cp * (double(p[b * T + i]) - mp)) : 0.f;
+    return;
+  }
   for (int64_t i = int64_t(c) * kBwdChunk + threadIdx.x; i < i1; i += blockDim.x)
     gp[b * T + i] = float(ct * (double(t[b * T + i]) - mt) + cp * (double(p[b * T + i]) - mp));
+}
+
+// the plain SNR's gradient from the batch mean alone, in the arithmetic of sel_snr_bwd (k_snr_bwd)
+__global__ __launch_bounds__(256) void k_snr_bwd_var(const float* __restrict__ p, const float* __restrict__ t,
+                                                     int64_t B, int64_t T, const int64_t* __restrict__ lens, int cpr,
+                                                     const double* __restrict__ sums, const float* __restrict__ g,
+                                                     float* __restrict__ gp) {
+  const float eps = 1.1920928955078125e-07f;
+  const float gv = g[0] * (20.f / 2.302585092994046f) / float(B);
+  const int64_t b = blockIdx.x / cpr;
+  const int c = int(blockIdx.x % cpr);
+  const int64_t n = row_len(lens, b, T);
+  const float den = float(sums[2 * b + 1]) + eps;
+  const int64_t i1 = int64_t(c + 1) * kBwdChunk < T ? int64_t(c + 1) * kBwdChunk : T;
+  for (int64_t i = int64_t(c) * kBwdChunk + threadIdx.x; i < i1; i += blockDim.x)
+    gp[b * T + i] = i < n ? gv * (t[b * T + i] - p[b * T + i]) / den : 0.f;
 }
 
 // ---------------------------------------------------------------------------
@@ -165,8 +240,15 @@ __device__ __forceinline__ double stoi_window(int n) {
 inline int64_t stoi_frames(int64_t T) { return (T - kFrame) / kHop + 1; }
 
 // e_i = 20 log10(||w x[128 i : 128 i + 256]|| + EPS) of the clean signal: one wave per frame
+// frames of a ragged row: 0 below one frame
+__device__ __forceinline__ int stoi_row_frames(const int64_t* __restrict__ lens, int64_t b, int64_t T) {
+  const int64_t n = row_len(lens, b, T);
+  return n >= kFrame ? int((n - kFrame) / kHop + 1) : 0;
+}
+
+template <bool VAR>
 __global__ __launch_bounds__(256) void k_stoi_energy(const float* __restrict__ clean, int64_t T, int F,
-                                                     float* __restrict__ e) {
+                                                     const int64_t* __restrict__ lens, float* __restrict__ e) {
   __shared__ float w[kFrame];
   w[threadIdx.x] = float(stoi_window(threadIdx.x));
   __syncthreads();
@@ -174,6 +256,9 @@ __global__ __launch_bounds__(256) void k_stoi_energy(const float* __restrict__ c
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   const int64_t b = blockIdx.y;
   if (i >= F) return;
+  if constexpr (VAR) {
+    if (i >= stoi_row_frames(lens, b, T)) return;
+  }
   const float* __restrict__ x = clean + b * T + int64_t(i) * kHop;
   float s = 0.f;
 #pragma unroll
@@ -187,12 +272,16 @@ __global__ __launch_bounds__(256) void k_stoi_energy(const float* __restrict__ c
 
 // One wave per row: the maximum, then the kept frames' indices compacted in
 // order, 64 frames per round.  cnt = (frames, kept, M = kept - 1).
-__global__ __launch_bounds__(64) void k_stoi_mask(const float* __restrict__ e, int F, int* __restrict__ kidx,
+template <bool VAR>
+__global__ __launch_bounds__(64) void k_stoi_mask(const float* __restrict__ e, int Fs, int64_t T,
+                                                  const int64_t* __restrict__ lens, int* __restrict__ kidx,
                                                   int* __restrict__ cnt, int* __restrict__ info) {
   const int lane = threadIdx.x;
   const int64_t b = blockIdx.x;
-  const float* __restrict__ er = e + b * F;
-  int* __restrict__ kr = kidx + b * F;
+  const float* __restrict__ er = e + b * Fs;
+  int* __restrict__ kr = kidx + b * Fs;
+  int F = Fs;  // the row's own frame count; Fs stays the stride
+  if constexpr (VAR) F = stoi_row_frames(lens, b, T);
   float mx = -INFINITY;
   for (int i = lane; i < F; i += 64) mx = fmaxf(mx, er[i]);
 #pragma unroll
@@ -438,6 +527,7 @@ __global__ __launch_bounds__(64) void k_stoi_seg(const double* __restrict__ band
 }
 
 // d_b = sum_s seg / (15 J) (STOI) or / (30 J) (ESTOI), summed in segment order; 1e-5 when M < 30
+template <bool VAR>
 __global__ __launch_bounds__(256) void k_stoi_finish(const double* __restrict__ seg, const int* __restrict__ cnt,
                                                      int64_t B, int F, int extended, float* __restrict__ d,
                                                      float* __restrict__ mean) {
@@ -452,11 +542,60 @@ __global__ __launch_bounds__(256) void k_stoi_finish(const double* __restrict__ 
       for (int i = 0; i < J; ++i) s += seg[b * int64_t(F - kSeg) + i];
       v = s / (double(extended ? kSeg : kBands) * double(J));
     }
+    if constexpr (VAR) {
+      if (cnt[3 * b] == 0) v = NAN;  // a row below one frame
+    }
     d[b] = float(v);
     acc += v;
   }
   acc = block_sum<double>(acc, red);
   if (threadIdx.x == 0 && mean) mean[0] = float(acc / double(B));
+}
+
+// ---------------------------------------------------------------------------
+// Ragged MAE / MSE / Mel-L1: one block per row, fp64 sums in a
+// fixed order (a strided sum per thread over the counted elements in
+// (sub-row, element) order, then the block tree).  An empty row is NaN.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_rows_l1_l2(const float* __restrict__ a, const float* __restrict__ b,
+                                                    int64_t inner, int64_t stride, const int64_t* __restrict__ lens,
+                                                    float* __restrict__ l1, float* __restrict__ l2) {
+  __shared__ double red[16];
+  const int64_t row = blockIdx.x;
+  const int64_t n = row_len(lens, row, stride);
+  const float* __restrict__ ar = a + row * inner * stride;
+  const float* __restrict__ br = b + row * inner * stride;
+  double s1 = 0.0, s2 = 0.0;
+  for (int64_t r = 0; r < inner; ++r)
+    for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
+      const double d = double(ar[r * stride + i]) - double(br[r * stride + i]);
+      s1 += fabs(d);
+      s2 += d * d;
+    }
+  s1 = block_sum<double>(s1, red);
+  s2 = block_sum<double>(s2, red);
+  if (threadIdx.x == 0) {
+    const double cntd = double(inner) * double(n);
+    l1[row] = n > 0 ? float(s1 / cntd) : NAN;
+    l2[row] = n > 0 ? float(s2 / cntd) : NAN;
+  }
+}
+
+// means[0], means[1] = the batch means of the per-row values, fp64 in a fixed order
+__global__ __launch_bounds__(256) void k_rows_means2(const float* __restrict__ l1, const float* __restrict__ l2,
+                                                     int64_t B, float* __restrict__ means) {
+  __shared__ double red[16];
+  double a1 = 0.0, a2 = 0.0;
+  for (int64_t b = threadIdx.x; b < B; b += blockDim.x) {
+    a1 += double(l1[b]);
+    a2 += double(l2[b]);
+  }
+  a1 = block_sum<double>(a1, red);
+  a2 = block_sum<double>(a2, red);
+  if (threadIdx.x == 0) {
+    means[0] = float(a1 / double(B));
+    means[1] = float(a2 / double(B));
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -774,17 +913,28 @@ extern "C" {
 
 size_t sel_sdr_workspace(int64_t B) { return B > 0 ? size_t(B) * 6 * sizeof(double) : 0; }
 
-int sel_sdr_fwd(const float* pred, const float* target, int64_t B, int64_t T, int scale_invariant, int zero_mean,
-                float* vals, float* mean, void* ws, size_t ws_bytes, sel_stream_t stream) {
-  SEL_REQUIRE(pred && target && vals && mean && ws, SEL_ERR_ARG, "sel_sdr_fwd: null pointer");
-  SEL_REQUIRE(B > 0 && T > 0 && B <= (int64_t(1) << 30), SEL_ERR_ARG, "sel_sdr_fwd: bad shape");
-  SEL_REQUIRE((scale_invariant | zero_mean | 1) == 1, SEL_ERR_ARG, "sel_sdr_fwd: flags must be 0 or 1");
-  SEL_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, SEL_ERR_ARG, "sel_sdr_fwd: workspace not 8-byte aligned");
-  SEL_REQUIRE(ws_bytes >= sel_sdr_workspace(B), SEL_ERR_WORKSPACE, "sel_sdr_fwd: workspace too small");
+namespace {
+
+// sel_sdr_fwd and sel_sdr_fwd_var: lens == nullptr is the fixed-length call
+int sdr_fwd(const char* fn, const float* pred, const float* target, int64_t B, int64_t T, const int64_t* lens,
+            int scale_invariant, int zero_mean, float* vals, float* mean, void* ws, size_t ws_bytes,
+            sel_stream_t stream) {
+  SEL_REQUIRE(pred && target && vals && mean && ws, SEL_ERR_ARG, "%s: null pointer", fn);
+  SEL_REQUIRE(B > 0 && T > 0 && B <= (int64_t(1) << 30), SEL_ERR_ARG, "%s: bad shape", fn);
+  SEL_REQUIRE((scale_invariant | zero_mean | 1) == 1, SEL_ERR_ARG, "%s: flags must be 0 or 1", fn);
+  SEL_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, SEL_ERR_ARG, "%s: workspace not 8-byte aligned", fn);
+  SEL_REQUIRE(ws_bytes >= sel_sdr_workspace(B), SEL_ERR_WORKSPACE, "%s: workspace too small", fn);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   double* pairs = static_cast<double*>(ws);
   double* ext = pairs + 2 * B;
   if (!scale_invariant && !zero_mean) {
+    if (lens) {
+      hipLaunchKernelGGL(k_snr_sums_var, dim3(unsigned(B)), dim3(256), 0, s, pred, target, T, lens, pairs);
+      SEL_LAUNCH_CHECK();
+      hipLaunchKernelGGL(k_snr_finish_var, dim3(1), dim3(256), 0, s, pairs, B, T, lens, vals, mean);
+      SEL_LAUNCH_CHECK();
+      return SEL_OK;
+    }
     // the plain SNR is sel_snr_fwd itself (same sums, same mean), plus its per-row values
     const int rc = sel_snr_fwd(pred, target, B, T, pairs, mean, stream);
     if (rc != SEL_OK) return rc;
@@ -792,32 +942,82 @@ int sel_sdr_fwd(const float* pred, const float* target, int64_t B, int64_t T, in
     SEL_LAUNCH_CHECK();
     return SEL_OK;
   }
-  hipLaunchKernelGGL(k_sdr_sums, dim3(unsigned(B)), dim3(256), 0, s, pred, target, T, zero_mean, pairs, ext);
-  SEL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sdr_finish, dim3(1), dim3(256), 0, s, pairs, ext, B, scale_invariant, vals, mean);
+  if (lens) {
+    hipLaunchKernelGGL(k_sdr_sums<true>, dim3(unsigned(B)), dim3(256), 0, s, pred, target, T, lens, zero_mean, pairs,
+                       ext);
+    SEL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_sdr_finish<true>, dim3(1), dim3(256), 0, s, pairs, ext, B, T, lens, scale_invariant, vals,
+                       mean);
+  } else {
+    hipLaunchKernelGGL(k_sdr_sums<false>, dim3(unsigned(B)), dim3(256), 0, s, pred, target, T, lens, zero_mean, pairs,
+                       ext);
+    SEL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_sdr_finish<false>, dim3(1), dim3(256), 0, s, pairs, ext, B, T, lens, scale_invariant, vals,
+                       mean);
+  }
   SEL_LAUNCH_CHECK();
   return SEL_OK;
+}
+
+int sdr_bwd(const char* fn, const float* pred, const float* target, int64_t B, int64_t T, const int64_t* lens,
+            int scale_invariant, int zero_mean, const float* g_vals, const float* g_mean, float* g_pred,
+            const void* ws, size_t ws_bytes, sel_stream_t stream) {
+  SEL_REQUIRE(pred && target && g_pred && ws, SEL_ERR_ARG, "%s: null pointer", fn);
+  SEL_REQUIRE(g_vals || g_mean, SEL_ERR_ARG, "%s: no incoming gradient", fn);
+  SEL_REQUIRE(B > 0 && T > 0 && B <= (int64_t(1) << 30), SEL_ERR_ARG, "%s: bad shape", fn);
+  const int64_t cpr = (T + kBwdChunk - 1) / kBwdChunk;
+  SEL_REQUIRE(cpr <= (int64_t(1) << 30) / B, SEL_ERR_ARG, "%s: batch too large", fn);
+  SEL_REQUIRE((scale_invariant | zero_mean | 1) == 1, SEL_ERR_ARG, "%s: flags must be 0 or 1", fn);
+  SEL_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, SEL_ERR_ARG, "%s: workspace not 8-byte aligned", fn);
+  SEL_REQUIRE(ws_bytes >= sel_sdr_workspace(B), SEL_ERR_WORKSPACE, "%s: workspace too small", fn);
+  const double* pairs = static_cast<const double*>(ws);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (!scale_invariant && !zero_mean && !g_vals) {
+    if (!lens) return sel_snr_bwd(pred, target, B, T, pairs, g_mean, g_pred, stream);
+    hipLaunchKernelGGL(k_snr_bwd_var, dim3(unsigned(B * cpr)), dim3(256), 0, s, pred, target, B, T, lens, int(cpr),
+                       pairs, g_mean, g_pred);
+    SEL_LAUNCH_CHECK();
+    return SEL_OK;
+  }
+  if (lens)
+    hipLaunchKernelGGL(k_sdr_bwd<true>, dim3(unsigned(B * cpr)), dim3(256), 0, s, pred, target, B, T, lens, int(cpr),
+                       scale_invariant, zero_mean, pairs, pairs + 2 * B, g_vals, g_mean, g_pred);
+  else
+    hipLaunchKernelGGL(k_sdr_bwd<false>, dim3(unsigned(B * cpr)), dim3(256), 0, s, pred, target, B, T, lens, int(cpr),
+                       scale_invariant, zero_mean, pairs, pairs + 2 * B, g_vals, g_mean, g_pred);
+  SEL_LAUNCH_CHECK();
+  return SEL_OK;
+}
+
+}  // namespace
+
+int sel_sdr_fwd(const float* pred, const float* target, int64_t B, int64_t T, int scale_invariant, int zero_mean,
+                float* vals, float* mean, void* ws, size_t ws_bytes, sel_stream_t stream) {
+  return sdr_fwd("sel_sdr_fwd", pred, target, B, T, nullptr, scale_invariant, zero_mean, vals, mean, ws, ws_bytes,
+                 stream);
+}
+
+int sel_sdr_fwd_var(const float* pred, const float* target, int64_t B, int64_t T, const int64_t* lengths,
+                    int scale_invariant, int zero_mean, float* vals, float* mean, void* ws, size_t ws_bytes,
+                    sel_stream_t stream) {
+  SEL_REQUIRE(lengths, SEL_ERR_ARG, "sel_sdr_fwd_var: null lengths");
+  return sdr_fwd("sel_sdr_fwd_var", pred, target, B, T, lengths, scale_invariant, zero_mean, vals, mean, ws, ws_bytes,
+                 stream);
 }
 
 int sel_sdr_bwd(const float* pred, const float* target, int64_t B, int64_t T, int scale_invariant, int zero_mean,
                 const float* g_vals, const float* g_mean, float* g_pred, const void* ws, size_t ws_bytes,
                 sel_stream_t stream) {
-  SEL_REQUIRE(pred && target && g_pred && ws, SEL_ERR_ARG, "sel_sdr_bwd: null pointer");
-  SEL_REQUIRE(g_vals || g_mean, SEL_ERR_ARG, "sel_sdr_bwd: no incoming gradient");
-  SEL_REQUIRE(B > 0 && T > 0 && B <= (int64_t(1) << 30), SEL_ERR_ARG, "sel_sdr_bwd: bad shape");
-  const int64_t cpr = (T + kBwdChunk - 1) / kBwdChunk;
-  SEL_REQUIRE(cpr <= (int64_t(1) << 30) / B, SEL_ERR_ARG, "sel_sdr_bwd: batch too large");
-  SEL_REQUIRE((scale_invariant | zero_mean | 1) == 1, SEL_ERR_ARG, "sel_sdr_bwd: flags must be 0 or 1");
-  SEL_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, SEL_ERR_ARG, "sel_sdr_bwd: workspace not 8-byte aligned");
-  SEL_REQUIRE(ws_bytes >= sel_sdr_workspace(B), SEL_ERR_WORKSPACE, "sel_sdr_bwd: workspace too small");
-  const double* pairs = static_cast<const double*>(ws);
-  if (!scale_invariant && !zero_mean && !g_vals)
-    return sel_snr_bwd(pred, target, B, T, pairs, g_mean, g_pred, stream);
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL(k_sdr_bwd, dim3(unsigned(B * cpr)), dim3(256), 0, s, pred, target, B, T, int(cpr),
-                     scale_invariant, zero_mean, pairs, pairs + 2 * B, g_vals, g_mean, g_pred);
-  SEL_LAUNCH_CHECK();
-  return SEL_OK;
+  return sdr_bwd("sel_sdr_bwd", pred, target, B, T, nullptr, scale_invariant, zero_mean, g_vals, g_mean, g_pred, ws,
+                 ws_bytes, stream);
+}
+
+int sel_sdr_bwd_var(const float* pred, const float* target, int64_t B, int64_t T, const int64_t* lengths,
+                    int scale_invariant, int zero_mean, const float* g_vals, const float* g_mean, float* g_pred,
+                    const void* ws, size_t ws_bytes, sel_stream_t stream) {
+  SEL_REQUIRE(lengths, SEL_ERR_ARG, "sel_sdr_bwd_var: null lengths");
+  return sdr_bwd("sel_sdr_bwd_var", pred, target, B, T, lengths, scale_invariant, zero_mean, g_vals, g_mean, g_pred,
+                 ws, ws_bytes, stream);
 }
 
 int sel_stoi_band_edges(int* edges) {
@@ -835,14 +1035,19 @@ size_t sel_stoi_workspace(int64_t B, int64_t T) {
   return size_t(B) * ((J + 2 * (F - 1) * kBands) * sizeof(double) + (2 * F + 3) * sizeof(float));
 }
 
-int sel_stoi(const float* clean, const float* proc, int64_t B, int64_t T, int extended, float* d, float* mean,
-             int* info, void* ws, size_t ws_bytes, sel_stream_t stream) {
-  SEL_REQUIRE(clean && proc && d && ws, SEL_ERR_ARG, "sel_stoi: null pointer");
-  SEL_REQUIRE(B > 0 && B <= 65535, SEL_ERR_ARG, "sel_stoi: B must be in [1, 65535]");
-  SEL_REQUIRE(T >= kFrame && T <= (int64_t(1) << 30), SEL_ERR_ARG, "sel_stoi: T must be in [256, 2^30]");
-  SEL_REQUIRE((extended | 1) == 1, SEL_ERR_ARG, "sel_stoi: extended must be 0 or 1");
-  SEL_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, SEL_ERR_ARG, "sel_stoi: workspace not 8-byte aligned");
-  SEL_REQUIRE(ws_bytes >= sel_stoi_workspace(B, T), SEL_ERR_WORKSPACE, "sel_stoi: workspace too small");
+namespace {
+
+// sel_stoi and sel_stoi_var: lens == nullptr is the fixed-length call.  With
+// lengths the strides (frames F, bands F - 1, segments F - 30) and the J > 0
+// launch skip still come from T; each row's own frame count is device data.
+int stoi_fwd(const char* fn, const float* clean, const float* proc, int64_t B, int64_t T, const int64_t* lens,
+             int extended, float* d, float* mean, int* info, void* ws, size_t ws_bytes, sel_stream_t stream) {
+  SEL_REQUIRE(clean && proc && d && ws, SEL_ERR_ARG, "%s: null pointer", fn);
+  SEL_REQUIRE(B > 0 && B <= 65535, SEL_ERR_ARG, "%s: B must be in [1, 65535]", fn);
+  SEL_REQUIRE(T >= kFrame && T <= (int64_t(1) << 30), SEL_ERR_ARG, "%s: T must be in [256, 2^30]", fn);
+  SEL_REQUIRE((extended | 1) == 1, SEL_ERR_ARG, "%s: extended must be 0 or 1", fn);
+  SEL_REQUIRE(reinterpret_cast<uintptr_t>(ws) % 8 == 0, SEL_ERR_ARG, "%s: workspace not 8-byte aligned", fn);
+  SEL_REQUIRE(ws_bytes >= sel_stoi_workspace(B, T), SEL_ERR_WORKSPACE, "%s: workspace too small", fn);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const int F = int(stoi_frames(T));
   const int J = F > kSeg ? F - kSeg : 0;
@@ -851,9 +1056,16 @@ int sel_stoi(const float* clean, const float* proc, int64_t B, int64_t T, int ex
   float* e = reinterpret_cast<float*>(bands + size_t(B) * 2 * (F - 1) * kBands);
   int* kidx = reinterpret_cast<int*>(e + size_t(B) * F);
   int* cnt = kidx + size_t(B) * F;
-  hipLaunchKernelGGL(k_stoi_energy, dim3(unsigned((F + 3) / 4), unsigned(B)), dim3(256), 0, s, clean, T, F, e);
-  SEL_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_stoi_mask, dim3(unsigned(B)), dim3(64), 0, s, e, F, kidx, cnt, info);
+  const dim3 eg(unsigned((F + 3) / 4), unsigned(B));
+  if (lens) {
+    hipLaunchKernelGGL(k_stoi_energy<true>, eg, dim3(256), 0, s, clean, T, F, lens, e);
+    SEL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_stoi_mask<true>, dim3(unsigned(B)), dim3(64), 0, s, e, F, T, lens, kidx, cnt, info);
+  } else {
+    hipLaunchKernelGGL(k_stoi_energy<false>, eg, dim3(256), 0, s, clean, T, F, lens, e);
+    SEL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_stoi_mask<false>, dim3(unsigned(B)), dim3(64), 0, s, e, F, T, lens, kidx, cnt, info);
+  }
   SEL_LAUNCH_CHECK();
   if (J > 0) {  // fewer than 31 frames cannot give M >= 30: every row is 1e-5
     hipLaunchKernelGGL(k_stoi_bands, dim3(unsigned(F - 1), unsigned(B)), dim3(64), 0, s, clean, proc, T, F, kidx, cnt,
@@ -862,8 +1074,43 @@ int sel_stoi(const float* clean, const float* proc, int64_t B, int64_t T, int ex
     hipLaunchKernelGGL(k_stoi_seg, dim3(unsigned(J), unsigned(B)), dim3(64), 0, s, bands, cnt, F, extended, seg);
     SEL_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(k_stoi_finish, dim3(1), dim3(256), 0, s, seg, cnt, B, F, extended, d, mean);
+  if (lens)
+    hipLaunchKernelGGL(k_stoi_finish<true>, dim3(1), dim3(256), 0, s, seg, cnt, B, F, extended, d, mean);
+  else
+    hipLaunchKernelGGL(k_stoi_finish<false>, dim3(1), dim3(256), 0, s, seg, cnt, B, F, extended, d, mean);
   SEL_LAUNCH_CHECK();
+  return SEL_OK;
+}
+
+}  // namespace
+
+int sel_stoi(const float* clean, const float* proc, int64_t B, int64_t T, int extended, float* d, float* mean,
+             int* info, void* ws, size_t ws_bytes, sel_stream_t stream) {
+  return stoi_fwd("sel_stoi", clean, proc, B, T, nullptr, extended, d, mean, info, ws, ws_bytes, stream);
+}
+
+int sel_stoi_var(const float* clean, const float* proc, int64_t B, int64_t T, const int64_t* lengths, int extended,
+                 float* d, float* mean, int* info, void* ws, size_t ws_bytes, sel_stream_t stream) {
+  SEL_REQUIRE(lengths, SEL_ERR_ARG, "sel_stoi_var: null lengths");
+  return stoi_fwd("sel_stoi_var", clean, proc, B, T, lengths, extended, d, mean, info, ws, ws_bytes, stream);
+}
+
+// Per-row mean |a - b| and mean (a - b)^2 of a ragged batch: row b is `inner`
+// sub-rows of `stride` elements, of which the first n[b] count.
+int sel_rows_l1_l2_var(const float* a, const float* b, int64_t B, int64_t inner, int64_t stride, const int64_t* n,
+                       float* l1, float* l2, float* means, sel_stream_t stream) {
+  SEL_REQUIRE(a && b && n && l1 && l2, SEL_ERR_ARG, "sel_rows_l1_l2_var: null pointer");
+  SEL_REQUIRE(B > 0 && B <= (int64_t(1) << 30) && inner > 0 && stride > 0, SEL_ERR_ARG,
+              "sel_rows_l1_l2_var: bad shape");
+  SEL_REQUIRE(inner <= (int64_t(1) << 40) / stride && B <= (int64_t(1) << 60) / (inner * stride), SEL_ERR_ARG,
+              "sel_rows_l1_l2_var: batch too large");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_rows_l1_l2, dim3(unsigned(B)), dim3(256), 0, s, a, b, inner, stride, n, l1, l2);
+  SEL_LAUNCH_CHECK();
+  if (means) {
+    hipLaunchKernelGGL(k_rows_means2, dim3(1), dim3(256), 0, s, l1, l2, B, means);
+    SEL_LAUNCH_CHECK();
+  }
   return SEL_OK;
 }
 

@@ -75,6 +75,50 @@ __global__ __launch_bounds__(256) void k_resample(const float* __restrict__ x, i
   y[wav * out_len + j] = acc;
 }
 
+// Ragged batches: row `wav` is a signal of lengths[wav] samples
+// (above `len` counts as `len`, negative as 0) in a row of stride `len`.  Each
+// output takes k_resample's path for a signal of that length, so taps past the
+// row's end are skipped and the row's bits are those of a call on the row
+// alone; outputs at and past the row's own output length are written as zero.
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_resample_var(const float* __restrict__ x, int64_t stride,
+                                                      const int64_t* __restrict__ lens, Plan p,
+                                                      const float* __restrict__ table, int64_t out_stride,
+                                                      float* __restrict__ y, int64_t* __restrict__ out_lens) {
+  extern __shared__ float taps_lds[];
+  const float* taps = table;
+  if constexpr (LDS) {
+    const int tsize = p.n * p.taps;
+    for (int i = threadIdx.x; i < tsize; i += blockDim.x) taps_lds[i] = table[i];
+    __syncthreads();
+    taps = taps_lds;
+  }
+  const int64_t wav = blockIdx.y;
+  int64_t len = lens[wav];
+  len = len > stride ? stride : (len < 0 ? 0 : len);
+  const int64_t out_len = (int64_t(p.n) * len + p.o - 1) / p.o;  // sel_resample_out_len
+  const int64_t j = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (j == 0) out_lens[wav] = out_len;
+  if (j >= out_stride) return;
+  float acc = 0.f;
+  if (j < out_len) {
+    const int64_t f = j / p.n;
+    const int ph = int(j - f * p.n);
+    const float* xs = x + wav * stride;
+    const float* k = taps + ph * p.taps;
+    const int64_t s0 = f * p.o - p.w;
+    if (s0 >= 0 && s0 + p.taps <= len) {
+      for (int i = 0; i < p.taps; ++i) acc = fmaf(xs[s0 + i], k[i], acc);
+    } else {
+      for (int i = 0; i < p.taps; ++i) {
+        const int64_t s = s0 + i;
+        if (s >= 0 && s < len) acc = fmaf(xs[s], k[i], acc);
+      }
+    }
+  }
+  y[wav * out_stride + j] = acc;
+}
+
 // The transpose, as a gather: one thread per input sample s sums gy[f n + p] *
 // K[p][s - f o + w] over the output frames f whose window [f o - w, f o + w + o)
 // contains s and their phases p, in ascending (f, p); no atomics.
@@ -173,6 +217,32 @@ int sel_resample(const float* x, int64_t n_wavs, int64_t len, int orig_freq, int
                        out_len, y);
   else
     hipLaunchKernelGGL(k_resample<false>, grid, dim3(256), 0, s, x, len, p, table, out_len, y);
+  SEL_LAUNCH_CHECK();
+  return SEL_OK;
+}
+
+/* the argument checks come first, so they can be seen without a device */
+int sel_resample_var(const float* x, int64_t n_wavs, int64_t len, const int64_t* lengths, int orig_freq, int new_freq,
+                     int lowpass_filter_width, float rolloff, const float* table, float* y, int64_t* out_lengths,
+                     sel_stream_t stream) {
+  int nph, ntaps;
+  if (int rc = sel_resample_plan(orig_freq, new_freq, lowpass_filter_width, rolloff, &nph, &ntaps)) return rc;
+  SEL_REQUIRE(x && lengths && table && y && out_lengths, SEL_ERR_ARG, "sel_resample_var: null pointer");
+  SEL_REQUIRE(n_wavs > 0 && len > 0 && len <= (int64_t(1) << 40), SEL_ERR_ARG,
+              "sel_resample_var: bad waveform shape (%lld, %lld)", (long long)n_wavs, (long long)len);
+  SEL_REQUIRE(n_wavs <= 65535, SEL_ERR_UNSUPPORTED, "sel_resample_var: at most 65535 waveforms per call");
+  SEL_REQUIRE(initialized(), SEL_ERR_STATE, "sel_init() has not succeeded");
+  const Plan p = plan(orig_freq, new_freq, lowpass_filter_width, rolloff);
+  const int64_t out_len = sel_resample_out_len(len, orig_freq, new_freq);
+  SEL_REQUIRE((out_len + 255) / 256 < (int64_t(1) << 31), SEL_ERR_ARG, "sel_resample_var: output too long");
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  dim3 grid(unsigned((out_len + 255) / 256), unsigned(n_wavs));
+  if (p.n * p.taps <= kLdsTable)
+    hipLaunchKernelGGL(k_resample_var<true>, grid, dim3(256), size_t(p.n) * p.taps * sizeof(float), s, x, len,
+                       lengths, p, table, out_len, y, out_lengths);
+  else
+    hipLaunchKernelGGL(k_resample_var<false>, grid, dim3(256), 0, s, x, len, lengths, p, table, out_len, y,
+                       out_lengths);
   SEL_LAUNCH_CHECK();
   return SEL_OK;
 }

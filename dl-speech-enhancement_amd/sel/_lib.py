@@ -100,6 +100,13 @@ SIGNATURES = {
     "sel_bss_sdr_chunk": (I64, []),
     "sel_bss_sdr_workspace": (SZ, [I64, I64, I32]),
     "sel_bss_sdr": (I32, [P, P, I64, I64, I32, I32, F64, P, P, P, P, SZ, P]),
+    "sel_sdr_fwd_var": (I32, [P, P, I64, I64, P, I32, I32, P, P, P, SZ, P]),
+    "sel_sdr_bwd_var": (I32, [P, P, I64, I64, P, I32, I32, P, P, P, P, SZ, P]),
+    "sel_stoi_var": (I32, [P, P, I64, I64, P, I32, P, P, P, P, SZ, P]),
+    "sel_bss_sdr_var": (I32, [P, P, I64, I64, P, I32, I32, F64, P, P, P, P, SZ, P]),
+    "sel_resample_var": (I32, [P, I64, I64, P, I32, I32, I32, F32, P, P, P, P]),
+    "sel_power_mel_fwd_var": (I32, [P, I64, I64, P, I32, I32, I32, P, P, P, I32, F32, P, P, P]),
+    "sel_rows_l1_l2_var": (I32, [P, P, I64, I64, I64, P, P, P, P, P]),
     "sel_batchnorm_workspace": (SZ, [I64, I32]),
     "sel_batchnorm_fwd": (I32, [P, I64, I32, P, P, I32, F32, F32, P, P, P, P, P, P, SZ, P]),
     "sel_batchnorm_bwd": (I32, [P, P, I64, I32, P, P, P, I32, P, P, P, P, SZ, P]),
@@ -268,6 +275,33 @@ def need_device(*tensors):
         if not t.is_cuda:
             raise SelError("sel: the MI355X path needs ROCm device tensors (got a CPU tensor); "
                            "there is no CPU fallback")
+
+
+def check_host_lengths(lengths, B, T, minimum, what):
+    """Per-row lengths given on the host (a sequence or a CPU tensor): B integers
+    in [minimum, T], as a CPU int64 tensor; anything else is a ValueError."""
+    t = torch.as_tensor(lengths)
+    if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+        raise ValueError(f"{what}: lengths must be integers, got {t.dtype}")
+    t = t.reshape(-1).to(torch.int64)
+    if t.numel() != B:
+        raise ValueError(f"{what}: {t.numel()} lengths for {B} rows")
+    if B and (int(t.min()) < minimum or int(t.max()) > T):
+        raise ValueError(f"{what}: lengths must be in [{minimum}, {T}], got [{int(t.min())}, {int(t.max())}]")
+    return t
+
+
+def lengths_arg(lengths, B, T, minimum, device, what):
+    """The device int64 array the *_var entry points take.  A device tensor is
+    used as it is, with no host read (a captured call then serves batches of
+    other lengths; out-of-range values follow the device contract of DESIGN
+    §25); host lengths are checked against [minimum, T] and copied."""
+    if torch.is_tensor(lengths) and lengths.is_cuda:
+        if lengths.dtype != torch.int64 or lengths.numel() != B:
+            raise ValueError(f"{what}: device lengths must be {B} int64 values, got {lengths.numel()} of "
+                             f"{lengths.dtype}")
+        return lengths.reshape(-1).contiguous()
+    return check_host_lengths(lengths, B, T, minimum, what).to(device)
 
 
 def workspace(nbytes, device):

@@ -29,6 +29,18 @@ SignalDistortionRatio(use_cg_iter=None, filter_length=512, zero_mean=False, load
     silent target row is NaN (torchmetrics raises there).  At T < filter_length
     torchmetrics' FFT reads wrapped lags; here the correlations stay linear.
 
+Ragged batches: snr, si_sdr, sdr and stoi and the four modules'
+forward take lengths=None.  With lengths, row b of the (..., T) input is its
+first lengths[b] samples and nothing past them is read (the padding may hold
+anything); the per-row values have the bits of a call on that row alone and a
+module returns the mean of the per-row values.  A device int64 tensor is used as
+it is, with no host read, so a captured call serves batches of other lengths: a
+value above T counts as T and a row below the measure's minimum (1 sample; 256
+for STOI at 10 kHz) is NaN.  A host sequence or CPU tensor is checked against
+[minimum, T] (ValueError) and copied.  snr and si_sdr keep autograd with lengths
+(exact zeros in the gradient at and past lengths[b]); STOI with lengths is
+forward only (stoi_loss_values takes none).
+
 All of them differentiate with respect to preds only (the target is data), and
 refuse CPU tensors like the rest of the package.  The functional forms snr,
 si_sdr, sdr and stoi return the per-row values (shape preds.shape[:-1]).
@@ -106,17 +118,96 @@ class _SDRFn(torch.autograd.Function):
         return gp.view(ctx.shape), None, None, None
 
 
-def snr(preds, target, zero_mean=False):
+def _rows(preds, target):
+    if preds.shape != target.shape:
+        raise ValueError(f"sel.metrics: preds {tuple(preds.shape)} and target {tuple(target.shape)} differ in shape")
+    T = preds.shape[-1]
+    return (preds.numel() // T if T else 0), T
+
+
+class _SDRVarFn(torch.autograd.Function):
+    """_SDRFn over a ragged batch: lens is the device int64 array of sel_sdr_fwd_var / sel_sdr_bwd_var."""
+
+    @staticmethod
+    def forward(ctx, pred, target, lens, scale_invariant, zero_mean):
+        T = pred.shape[-1]
+        p = pred.contiguous().float().reshape(-1, T)
+        t = target.contiguous().float().reshape(-1, T)
+        B = p.shape[0]
+        ws = L.workspace(L.lib().sel_sdr_workspace(B), p.device)
+        vals = torch.empty(B, dtype=torch.float32, device=p.device)
+        mean = torch.empty((), dtype=torch.float32, device=p.device)
+        L.call("sel_sdr_fwd_var", L.ptr(p), L.ptr(t), B, T, L.ptr(lens), int(scale_invariant), int(zero_mean),
+               L.ptr(vals), L.ptr(mean), L.ptr(ws), ws.numel(), L.stream())
+        ctx.save_for_backward(p, t, lens, ws)
+        ctx.shape = pred.shape
+        ctx.flags = (int(scale_invariant), int(zero_mean))
+        ctx.set_materialize_grads(False)
+        return vals.view(pred.shape[:-1]), mean
+
+    @staticmethod
+    def backward(ctx, g_vals, g_mean):
+        p, t, lens, ws = ctx.saved_tensors
+        if g_vals is None and g_mean is None:
+            return None, None, None, None, None
+        B, T = p.shape
+        gv = g_vals.contiguous().float().reshape(-1) if g_vals is not None else None
+        gm = g_mean.contiguous().float() if g_mean is not None else None
+        gp = torch.empty_like(p)
+        L.call("sel_sdr_bwd_var", L.ptr(p), L.ptr(t), B, T, L.ptr(lens), ctx.flags[0], ctx.flags[1], L.ptr(gv),
+               L.ptr(gm), L.ptr(gp), L.ptr(ws), ws.numel(), L.stream())
+        return gp.view(ctx.shape), None, None, None, None
+
+
+def _sdr_family(preds, target, scale_invariant, zero_mean, lengths):
+    if lengths is None:
+        return _SDRFn.apply(preds, target, scale_invariant, zero_mean)
+    B, T = _rows(preds, target)
+    lens = L.lengths_arg(lengths, B, T, 1, preds.device, "sel.metrics")
+    L.need_device(preds, target)
+    return _SDRVarFn.apply(preds, target, lens, scale_invariant, zero_mean)
+
+
+def snr(preds, target, zero_mean=False, lengths=None):
     """Per-row SNR in dB (torchmetrics.functional.signal_noise_ratio)."""
-    return _SDRFn.apply(preds, target, False, bool(zero_mean))[0]
+    return _sdr_family(preds, target, False, bool(zero_mean), lengths)[0]
 
 
-def si_sdr(preds, target, zero_mean=False):
+def si_sdr(preds, target, zero_mean=False, lengths=None):
     """Per-row SI-SDR in dB (torchmetrics.functional.scale_invariant_signal_distortion_ratio)."""
-    return _SDRFn.apply(preds, target, True, bool(zero_mean))[0]
+    return _sdr_family(preds, target, True, bool(zero_mean), lengths)[0]
 
 
-def _stoi(preds, target, fs, extended):
+def stoi_min_length(fs):
+    """The shortest signal at rate fs that gives one STOI frame (256 samples at 10 kHz)."""
+    g = math.gcd(int(fs), STOI_FS)
+    o, n = int(fs) // g, STOI_FS // g
+    return 255 * o // n + 1  # smallest len with ceil(n len / o) >= 256
+
+
+def _stoi_var(preds, target, fs, extended, lengths, info=None):
+    B, T = _rows(preds, target)
+    lens = L.lengths_arg(lengths, B, T, stoi_min_length(fs), preds.device, "sel.metrics")
+    L.need_device(preds, target)
+    shape = preds.shape[:-1]
+    if int(fs) != STOI_FS:  # both signals through the ragged resampler, on the device lengths
+        preds, out_lens = resample(preds, int(fs), STOI_FS, lengths=lens)
+        target, _ = resample(target, int(fs), STOI_FS, lengths=lens)
+        lens = out_lens
+    T = preds.shape[-1]
+    p = preds.detach().contiguous().float().reshape(-1, T)
+    t = target.detach().contiguous().float().reshape(-1, T)
+    ws = L.workspace(L.lib().sel_stoi_workspace(B, T), p.device)
+    d = torch.empty(B, dtype=torch.float32, device=p.device)
+    mean = torch.empty((), dtype=torch.float32, device=p.device)
+    L.call("sel_stoi_var", L.ptr(t), L.ptr(p), B, T, L.ptr(lens), int(bool(extended)), L.ptr(d), L.ptr(mean),
+           L.ptr(info), L.ptr(ws), ws.numel(), L.stream())
+    return d.view(shape), mean
+
+
+def _stoi(preds, target, fs, extended, lengths=None):
+    if lengths is not None:
+        return _stoi_var(preds, target, fs, extended, lengths)
     L.need_device(preds, target)
     if preds.shape != target.shape:
         raise ValueError(f"sel.metrics: preds {tuple(preds.shape)} and target {tuple(target.shape)} differ in shape")
@@ -135,9 +226,9 @@ def _stoi(preds, target, fs, extended):
 
 
 @torch.no_grad()
-def stoi(preds, target, fs, extended=False):
+def stoi(preds, target, fs, extended=False, lengths=None):
     """Per-row STOI (ESTOI with extended=True); `target` is the clean signal."""
-    return _stoi(preds, target, fs, extended)[0]
+    return _stoi(preds, target, fs, extended, lengths)[0]
 
 
 class _STOIFn(torch.autograd.Function):
@@ -197,6 +288,29 @@ def stoi_loss_values(preds, target, fs, extended=False):
     return _stoi_grad(preds, target, fs, extended)[0]
 
 
+def rows_l1_l2(a, b, n, means=False):
+    """Per-row mean |a - b| and mean (a - b)^2 of a ragged batch (sel_rows_l1_l2_var):
+    a, b (B, stride) or (B, inner, stride) fp32 on the device, of which the first
+    n[b] elements of every sub-row count; n a device int64 tensor.  fp64 sums in a
+    fixed order.  With means=True also the (2,) batch means of the two."""
+    L.need_device(a, b, n)
+    if a.shape != b.shape or a.dim() not in (2, 3):
+        raise ValueError(f"sel.metrics: rows_l1_l2 needs two (B, stride) or (B, inner, stride) tensors, got "
+                         f"{tuple(a.shape)} and {tuple(b.shape)}")
+    B, stride = a.shape[0], a.shape[-1]
+    inner = a.shape[1] if a.dim() == 3 else 1
+    if n.dtype != torch.int64 or n.numel() != B:
+        raise ValueError(f"sel.metrics: rows_l1_l2 needs {B} int64 counts")
+    a = a.detach().contiguous().float()
+    b = b.detach().contiguous().float()
+    l1 = torch.empty(B, dtype=torch.float32, device=a.device)
+    l2 = torch.empty(B, dtype=torch.float32, device=a.device)
+    m = torch.empty(2, dtype=torch.float32, device=a.device) if means else None
+    L.call("sel_rows_l1_l2_var", L.ptr(a), L.ptr(b), B, inner, stride, L.ptr(n.contiguous()), L.ptr(l1), L.ptr(l2),
+           L.ptr(m), L.stream())
+    return (l1, l2, m) if means else (l1, l2)
+
+
 _warned_cg = False
 
 
@@ -215,7 +329,11 @@ def _check_sdr_args(use_cg_iter, filter_length, load_diag):
     return int(filter_length), 0.0 if load_diag is None else float(load_diag)
 
 
-def _bss_sdr(preds, target, filter_length, zero_mean, load_diag):
+def _bss_sdr(preds, target, filter_length, zero_mean, load_diag, lengths=None, corr=None):
+    lens = None
+    if lengths is not None:
+        B, T = _rows(preds, target)
+        lens = L.lengths_arg(lengths, B, T, 1, preds.device, "sel.metrics")
     L.need_device(preds, target)
     if preds.shape != target.shape:
         raise ValueError(f"sel.metrics: preds {tuple(preds.shape)} and target {tuple(target.shape)} differ in shape")
@@ -226,17 +344,21 @@ def _bss_sdr(preds, target, filter_length, zero_mean, load_diag):
     ws = L.workspace(L.lib().sel_bss_sdr_workspace(B, T, filter_length), p.device)
     vals = torch.empty(B, dtype=torch.float32, device=p.device)
     mean = torch.empty((), dtype=torch.float32, device=p.device)
-    L.call("sel_bss_sdr", L.ptr(p), L.ptr(t), B, T, filter_length, int(bool(zero_mean)), load_diag, L.ptr(vals),
-           L.ptr(mean), None, L.ptr(ws), ws.numel(), L.stream())
+    if lens is None:
+        L.call("sel_bss_sdr", L.ptr(p), L.ptr(t), B, T, filter_length, int(bool(zero_mean)), load_diag, L.ptr(vals),
+               L.ptr(mean), L.ptr(corr), L.ptr(ws), ws.numel(), L.stream())
+    else:
+        L.call("sel_bss_sdr_var", L.ptr(p), L.ptr(t), B, T, L.ptr(lens), filter_length, int(bool(zero_mean)),
+               load_diag, L.ptr(vals), L.ptr(mean), L.ptr(corr), L.ptr(ws), ws.numel(), L.stream())
     return vals.view(preds.shape[:-1]), mean
 
 
 @torch.no_grad()
-def sdr(preds, target, use_cg_iter=None, filter_length=512, zero_mean=False, load_diag=None):
+def sdr(preds, target, use_cg_iter=None, filter_length=512, zero_mean=False, load_diag=None, lengths=None):
     """Per-row BSS-eval SDR in dB (torchmetrics.functional.signal_distortion_ratio,
     direct solve).  No autograd: the result carries no grad_fn."""
     filter_length, load_diag = _check_sdr_args(use_cg_iter, filter_length, load_diag)
-    return _bss_sdr(preds, target, filter_length, zero_mean, load_diag)[0]
+    return _bss_sdr(preds, target, filter_length, zero_mean, load_diag, lengths)[0]
 
 
 class SignalNoiseRatio(torch.nn.Module):
@@ -246,7 +368,9 @@ class SignalNoiseRatio(torch.nn.Module):
         super().__init__()
         self.zero_mean = bool(zero_mean)
 
-    def forward(self, preds, target):
+    def forward(self, preds, target, lengths=None):
+        if lengths is not None:
+            return _sdr_family(preds, target, False, self.zero_mean, lengths)[1]
         if self.zero_mean:
             return _SDRFn.apply(preds, target, False, True)[1]
         return _SNRFn.apply(preds, target)
@@ -259,8 +383,8 @@ class ScaleInvariantSignalDistortionRatio(torch.nn.Module):
         super().__init__()
         self.zero_mean = bool(zero_mean)
 
-    def forward(self, preds, target):
-        return _SDRFn.apply(preds, target, True, self.zero_mean)[1]
+    def forward(self, preds, target, lengths=None):
+        return _sdr_family(preds, target, True, self.zero_mean, lengths)[1]
 
 
 class SignalDistortionRatio(torch.nn.Module):
@@ -273,8 +397,8 @@ class SignalDistortionRatio(torch.nn.Module):
         self.zero_mean = bool(zero_mean)
 
     @torch.no_grad()
-    def forward(self, preds, target):
-        return _bss_sdr(preds, target, self.filter_length, self.zero_mean, self.load_diag)[1]
+    def forward(self, preds, target, lengths=None):
+        return _bss_sdr(preds, target, self.filter_length, self.zero_mean, self.load_diag, lengths)[1]
 
 
 class ShortTimeObjectiveIntelligibility(torch.nn.Module):
@@ -289,5 +413,5 @@ class ShortTimeObjectiveIntelligibility(torch.nn.Module):
         self.extended = bool(extended)
 
     @torch.no_grad()
-    def forward(self, preds, target):
-        return _stoi(preds, target, self.fs, self.extended)[1]
+    def forward(self, preds, target, lengths=None):
+        return _stoi(preds, target, self.fs, self.extended, lengths)[1]

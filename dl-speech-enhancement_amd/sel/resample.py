@@ -60,16 +60,47 @@ class _ResampleFn(torch.autograd.Function):
         return gx.view(shape).to(dtype), None, None, None, None
 
 
+def _resample_var(waveform, lengths, orig_freq, new_freq, lowpass_filter_width, rolloff):
+    shape = waveform.shape
+    T = shape[-1]
+    B = waveform.numel() // T if T else 0
+    lens = L.lengths_arg(lengths, B, T, 0, waveform.device, "sel.resample")
+    L.need_device(waveform)
+    if orig_freq == new_freq:
+        return waveform, lens.view(shape[:-1])
+    lib = L.lib()
+    g = math.gcd(int(orig_freq), int(new_freq))
+    o, n = int(orig_freq) // g, int(new_freq) // g
+    tab = _table_dev(o, n, int(lowpass_filter_width), float(rolloff), waveform.device)
+    x = waveform.detach().reshape(-1, T).float().contiguous()
+    out_len = lib.sel_resample_out_len(T, o, n)
+    y = torch.empty(B, out_len, dtype=torch.float32, device=x.device)
+    out_lens = torch.empty(B, dtype=torch.int64, device=x.device)
+    L.call("sel_resample_var", L.ptr(x), B, T, L.ptr(lens), o, n, int(lowpass_filter_width), float(rolloff),
+           L.ptr(tab), L.ptr(y), L.ptr(out_lens), L.stream())
+    return y.view(*shape[:-1], out_len), out_lens.view(shape[:-1])
+
+
 def resample(waveform, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99,
-             resampling_method="sinc_interp_hann", differentiable=False):
+             resampling_method="sinc_interp_hann", differentiable=False, lengths=None):
     """Drop-in for torchaudio.functional.resample (sinc_interp_hann): (..., time)
     fp32 on the device -> (..., ceil(time * new / orig)) with the reduced ratio.
     differentiable=True (not in torchaudio's signature): the result carries the
-    gradient to `waveform` through sel_resample_bwd; the default has no backward."""
+    gradient to `waveform` through sel_resample_bwd; the default has no backward.
+    lengths (not in torchaudio's signature): row b is resampled as a
+    signal of lengths[b] samples and the call returns (y, out_lengths): y is zero
+    at and past out_lengths[b] = ceil(lengths[b] * new / orig), a device int64
+    tensor computed on the device.  Device lengths are used as they are (a value
+    above time counts as time), host lengths are checked against [0, time].  No
+    backward with lengths."""
     if resampling_method not in ("sinc_interp_hann", "sinc_interpolation"):
         raise NotImplementedError(f"sel.resample: {resampling_method} is not implemented")
     if orig_freq <= 0 or new_freq <= 0:
         raise ValueError("Original frequency and desired frequecy should be positive")
+    if lengths is not None:
+        if differentiable:
+            raise NotImplementedError("sel.resample: lengths with differentiable=True is not implemented")
+        return _resample_var(waveform, lengths, int(orig_freq), int(new_freq), lowpass_filter_width, rolloff)
     if orig_freq == new_freq:
         return waveform
     L.need_device(waveform)

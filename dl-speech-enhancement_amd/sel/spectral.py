@@ -288,18 +288,29 @@ class MelL1(torch.autograd.Function):
         return gx, None, None, None, None, None, None, None, None, None, None
 
 
-def power_mel(x, n_fft, hop, win_length, window, fb, krange, power=2.0):
+def power_mel(x, n_fft, hop, win_length, window, fb, krange, power=2.0, lengths=None):
     """|STFT|^power @ fb (torchaudio MelSpectrogram semantics, mel_spectrogram.py:38).
     x (B, T) fp32 device -> (B, n_mels, 1 + T // hop).  Forward only: the reference
     uses it as an eval metric (Mel_L1), so a grad-requiring input is refused
-    rather than silently detached."""
+    rather than silently detached.  With lengths row b is its first
+    lengths[b] samples: the reflect pad mirrors about lengths[b] - 1, the row has
+    1 + lengths[b] // hop frames, the frames past them are zero, and the call
+    returns (out, frames) with frames the device int64 frame counts."""
     if torch.is_grad_enabled() and x.requires_grad:
         raise NotImplementedError("sel power_mel is forward-only (eval metric); call under torch.no_grad()")
     x = _signal_2d(x)
+    lens = None
+    if lengths is not None:
+        lens = L.lengths_arg(lengths, x.shape[0], x.shape[1], int(n_fft) // 2 + 1, x.device, "sel.spectral")
     L.need_device(x, window, fb, krange)
     B, T = x.shape
     n_mels = fb.shape[1]
     out = torch.empty(B, n_mels, _frames(T, hop), device=x.device, dtype=torch.float32)
+    if lens is not None:
+        frames = torch.empty(B, dtype=torch.int64, device=x.device)
+        L.call("sel_power_mel_fwd_var", L.ptr(x), B, T, L.ptr(lens), int(n_fft), int(hop), int(win_length),
+               L.ptr(window), L.ptr(fb), L.ptr(krange), n_mels, float(power), L.ptr(out), L.ptr(frames), L.stream())
+        return out, frames
     L.call("sel_power_mel_fwd", L.ptr(x), B, T, int(n_fft), int(hop), int(win_length), L.ptr(window),
            L.ptr(fb), L.ptr(krange), n_mels, float(power), L.ptr(out), L.stream())
     return out

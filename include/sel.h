@@ -768,6 +768,57 @@ int sel_bss_sdr(const float* pred, const float* target, int64_t B, int64_t T, in
                 double* corr /*(B, 2, filter_length), may be NULL*/, void* ws, size_t ws_bytes,
                 sel_stream_t stream);
 
+/* ---- ragged batches: per-row lengths through the measures ----
+ * lengths: a DEVICE array of B int64.  T stays the row stride and the largest
+ * length; row b is its first lengths[b] samples and nothing at or past
+ * lengths[b] influences any output (the padding may hold NaN).  The host never
+ * reads lengths, so the contract on its values is kept on the device: a value
+ * above T counts as T; a row shorter than the measure's minimum (1 for the SDR
+ * family, the BSS-eval SDR and rows_l1_l2; 256 for STOI; n_fft / 2 + 1 for
+ * power-mel) is NaN in that row and in the batch mean and leaves the other
+ * rows alone.  Each *_var call takes the arguments of its fixed-length form
+ * plus lengths, refuses what that form refuses (and null lengths) before any
+ * device work, uses the same workspace size, allocates nothing, never reads
+ * the device from the host, can be captured, uses no atomics and gives the
+ * same bits run to run.  Row b of a ragged call has the bits of the
+ * fixed-length call on that row alone at T = lengths[b]; the batch mean is the
+ * mean of the per-row values.
+ *   sel_sdr_bwd_var writes all of g_pred (B, T), exact zeros at and past lengths[b].
+ *   sel_stoi_var: (lengths[b] - 256) / 128 + 1 frames per row; info reports each
+ *     row's own (frames, kept, M).  Forward only.
+ *   sel_resample_var: row b is resampled as a signal of lengths[b] samples;
+ *     y (n_wavs, sel_resample_out_len(len, ...)) is zero at and past
+ *     out_lengths[b] = sel_resample_out_len(lengths[b], ...) (device, int64).
+ *   sel_power_mel_fwd_var: the reflect pad mirrors about lengths[b] - 1; row b
+ *     has frames[b] = 1 + lengths[b] / hop frames (device, int64), the frames of
+ *     out (B, n_mels, 1 + T / hop) past them are zero.
+ *   sel_rows_l1_l2_var: row b of a and b is `inner` sub-rows of `stride`
+ *     elements, of which the first n[b] count: l1[b] = mean |a - b|, l2[b] =
+ *     mean (a - b)^2 over inner * n[b] elements, fp64 sums in a fixed order;
+ *     means (2, may be NULL): the batch means of l1 and l2. */
+int sel_sdr_fwd_var(const float* pred, const float* target, int64_t B, int64_t T, const int64_t* lengths,
+                    int scale_invariant, int zero_mean, float* vals /*B*/, float* mean /*1*/, void* ws,
+                    size_t ws_bytes, sel_stream_t stream);
+int sel_sdr_bwd_var(const float* pred, const float* target, int64_t B, int64_t T, const int64_t* lengths,
+                    int scale_invariant, int zero_mean, const float* g_vals /*B, may be NULL*/,
+                    const float* g_mean /*1, may be NULL*/, float* g_pred, const void* ws, size_t ws_bytes,
+                    sel_stream_t stream);
+int sel_stoi_var(const float* clean, const float* proc, int64_t B, int64_t T, const int64_t* lengths, int extended,
+                 float* d /*B*/, float* mean /*1, may be NULL*/, int* info /*3B, may be NULL*/, void* ws,
+                 size_t ws_bytes, sel_stream_t stream);
+int sel_bss_sdr_var(const float* pred, const float* target, int64_t B, int64_t T, const int64_t* lengths,
+                    int filter_length, int zero_mean, double load_diag, float* vals /*B*/,
+                    float* mean /*1, may be NULL*/, double* corr /*(B, 2, filter_length), may be NULL*/, void* ws,
+                    size_t ws_bytes, sel_stream_t stream);
+int sel_resample_var(const float* x, int64_t n_wavs, int64_t len, const int64_t* lengths, int orig_freq,
+                     int new_freq, int lowpass_filter_width, float rolloff, const float* table, float* y,
+                     int64_t* out_lengths /*n_wavs*/, sel_stream_t stream);
+int sel_power_mel_fwd_var(const float* x, int64_t B, int64_t T, const int64_t* lengths, int n_fft, int hop,
+                          int win_length, const float* window, const float* fb, const int32_t* krange, int n_mels,
+                          float power, float* out, int64_t* frames /*B*/, sel_stream_t stream);
+int sel_rows_l1_l2_var(const float* a, const float* b, int64_t B, int64_t inner, int64_t stride, const int64_t* n,
+                       float* l1 /*B*/, float* l2 /*B*/, float* means /*2, may be NULL*/, sel_stream_t stream);
+
 /* ---- data pipeline: band-limited resampling ----
  * replaces torchaudio.functional.resample(x, orig, new) at dataloader/AudioDataset.py:28-33
  * (defaults: sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99; torchaudio 2.1.1
